@@ -8,7 +8,7 @@ By default successive steps are pipelined the way a service decoding one recordi
 (chain_execute.RecordingPipeline, --overlap 2): demod kernels, slicer streams and host stages of neighbouring steps overlap;
 all K steps complete inside the timed region.  --overlap 0 times them strictly one after the other.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--samples S] [--chains-per-gpu C]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--samples S] [--chains-per-gpu C] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Prints ONE JSON line on rank 0 with `roofline` (dominant GPU kernel, HIP-event time measured inside the timed region
@@ -19,12 +19,6 @@ import json
 import os
 import sys
 import time
-
-# Before anything loads the HIP runtime: eight hardware queues instead of the default four.  The executor keeps two demod and two slicer
-# streams busy; with an RCCL communicator (its streams made first) and torch's own in the same process, four queues made those streams
-# share queues and their kernels take turns -- the forced one-rank exchange ran at 1.02 ms per step against 0.77 without, and at
-# 0.80 with eight queues.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 import numpy as np
 
@@ -170,6 +164,9 @@ def main():
                     "more than 8192 loops, 131072 from 2048 recordings, else 262144 -- the work buffers are sized by it)")
     ap.add_argument("--also", type=int, default=1, help="1 (default, one GPU only): after the headline workload also measure fsk_9600, "
                     "bpsk_300 and qpsk_2400 (BASELINE configs[2], [1], [4]) briefly and attach them under 'also'")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline workload's last step returned (its packet table) to DIR/*.npy "
+                         "(see dump_outputs), for comparing the outputs of two builds")
     ap.add_argument("--with-exchange", type=int, default=1,
                     help="1 (default): a one-GPU line also carries value_with_exchange -- the same timed steps with the packet exchange "
                          "(one-rank RCCL gather + rank 0's de-dup over gathered rows) behind the executor, what every rank of an N > 1 run "
@@ -255,7 +252,7 @@ def main():
     coll_device = f"cuda:{dev_index}" if (use_dist and args.backend == "nccl") else None
 
     env = {"rank": rank, "world": world, "dev_index": dev_index, "use_dist": use_dist, "coll_device": coll_device}
-    out = measure(args, env)
+    out = measure(args, dict(env, dump_dir=args.dump_outputs))       # (the headline steps only: no other leg writes outputs)
     if os.environ.get("BENCH_EX_SKIP") and out is not None:   # a diagnostic that drops part of the exchange: the line is not a measurement
         out["invalid"] = "BENCH_EX_SKIP=" + os.environ["BENCH_EX_SKIP"] + ": part of the packet exchange was skipped"
     import copy
@@ -455,6 +452,51 @@ def also_workloads(args, env, cpu_also=None):
         except Exception as e:                                   # noqa: BLE001
             out.setdefault(name, {})["error"] = repr(e)[:300]
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+HEAD_FIELDS = ("streamaddress", "len", "bytes_corrected", "calculated_crc", "carried_crc", "valid_crc", "valid_header", "source_decoder",
+               "correlated_count")
+
+
+def dump_outputs(table, directory):
+    """--dump-outputs: what the timed path handed its caller for the last step -- the PacketTable of the last recording -- as .npy files:
+      packets_header.npy     float64 (rows, 10): row index in the table, then HEAD_FIELDS, one row per decoded packet, chain by chain
+      packets_payload.npy    float32: the payload bytes of those rows, concatenated in row order (`len` of each row delimits them)
+      chain_counts.npy       float64 (chains,): rows each chain decoded
+      unique_rows.npy        float64: table row index of every unique packet after the cross-chain de-dup, in the table's order
+      unique_decoders.npy    float32 (unique, chains): 1 where a chain decoded that unique packet
+    Everything is integer-valued and exact in its float type.  Past DUMP_LIMIT_BYTES in all, a fixed seeded sample of the rows is written
+    (the row index column says which)."""
+    os.makedirs(directory, exist_ok=True)
+    if table is None:
+        from pymodem_amd.packet_meta import PacketTable
+        table = PacketTable({}, [])
+    heads = table.heads
+    n, nchains = len(heads), len(table.counts)
+    uniq = np.zeros(0, np.int64) if table.unique_idx is None else np.asarray(table.unique_idx, np.int64)
+    decoders = np.zeros((len(uniq), nchains), np.float32)
+    if len(uniq):
+        index = {name: c for c, name in enumerate(table.names)}
+        for u, names in enumerate(table.unique_decoders):
+            decoders[u, [index[x] for x in names]] = 1.0
+    lens = heads["len"].astype(np.int64) if n else np.zeros(0, np.int64)
+    fixed = uniq.nbytes + decoders.nbytes + nchains * 8
+    keep = np.arange(n)
+    if n and fixed + n * 80 + int(lens.sum()) * 4 > DUMP_LIMIT_BYTES:
+        per_row = (n * 80 + int(lens.sum()) * 4) / n
+        m = max(1, int((DUMP_LIMIT_BYTES - fixed) / per_row))
+        keep = np.sort(np.random.default_rng(0).choice(n, size=min(m, n), replace=False))
+    header = np.empty((len(keep), 1 + len(HEAD_FIELDS)), np.float64)
+    header[:, 0] = keep
+    for j, f in enumerate(HEAD_FIELDS):
+        header[:, j + 1] = heads[f][keep] if len(keep) else 0
+    payload = np.frombuffer(b"".join(table.payload(int(i)) for i in keep), np.uint8).astype(np.float32)
+    np.save(os.path.join(directory, "packets_header.npy"), header)
+    np.save(os.path.join(directory, "packets_payload.npy"), payload)
+    np.save(os.path.join(directory, "chain_counts.npy"), np.asarray(table.counts, np.float64))
+    np.save(os.path.join(directory, "unique_rows.npy"), uniq.astype(np.float64))
+    np.save(os.path.join(directory, "unique_decoders.npy"), decoders)
 
 
 def measure(args, env):
@@ -1018,6 +1060,8 @@ def measure(args, env):
                 by[name][1] += d
         print("[thread cpu] ms per step by thread name (threads): " +
               ", ".join(f"{k} {v[1] / max(args.steps, 1) * 1e3:.2f} ({v[0]})" for k, v in sorted(by.items(), key=lambda kv: -kv[1][1])), file=sys.stderr)
+    if env.get("dump_dir") and rank == 0:
+        dump_outputs(result, env["dump_dir"])
     if os.environ.get("BENCH_NO_PROF"):                   # diagnostic: the step time without the HIP-event bracketing the roofline needs
         print(json.dumps({"ms_per_step_without_profiling": round(elapsed / args.steps * 1e3, 3), "stages": stage_ms}), file=sys.stderr)
         sys.exit(0)

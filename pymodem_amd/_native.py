@@ -306,9 +306,6 @@ def lib():
         if not os.path.exists(path):
             raise NativeError(f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                               "(hipcc --offload-arch=gfx950). pymodem_amd has no CPU fallback.")
-        # (takes effect when this is what loads the HIP runtime: streams of several libraries in one process -- RCCL, torch, ours -- share
-        # the default four hardware queues and serialise)
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
         handle = ctypes.CDLL(path)
         for name, (args, res) in _SIGS.items():
             fn = getattr(handle, name)      # AttributeError here = header and library out of sync
