@@ -38,6 +38,7 @@ struct pm_tuning {
     int slicer_max_chunk_words = 0, slicer_chunk_words = 0, slicer_quantum_words = 0;      // PM_SLICER_*_WORDS (0: the defaults)
     int slicer_compare_step = 0, slicer_mask_step = 0, slicer_compiled_step = 0;           // older forms of the slicer step
     int slicer_trace = 0, slicer_no_setprio = 0;
+    int slicer_no_event_step = 0, slicer_event_crossings = 0;                              // step32a everywhere / the event step's fallback threshold (0: default)
     int fir8 = 1;                      // PM_FIR8=0: the batch engine's matched filters in binary64 on the vector pipe
     int bpf8_max = 1;                  // PM_BPF8_MAX=0: the batch engine's pass for the AGC's `normal` as the reference's sums + a maximum
     int loop_agc = 1;                  // PM_LOOP_AGC=0: the batch engine's BPSK AGC as a pass of its own, not in the loop's lane

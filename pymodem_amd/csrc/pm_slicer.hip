@@ -20,13 +20,18 @@
 // launch has as many waves as there are walkers still on their way.  No crossings at all (digital silence) degrades to every
 // walker reaching the end of its stream: sequential depth, never a wrong answer.
 //
-// A lone wave pays both the loop-carried chain (add -> compare -> select -> multiply, ~45 cycles with the latencies measured
-// by tools/ubench) and the issue of the ~11 VALU instructions of a step (~5.5 cycles each): ~85 cycles per sample.
+// A lone wave of step32a pays the loop-carried chain and the issue of 8 VALU instructions per sample: ~60 cycles per sample alone
+// (1.57 us per word on digital silence).  The event step (pm_slicer_event.h, STEP 9-12) steps only the samples at which the recurrence
+// does more than an exact clk += 1.0 and takes the runs between them as one addition: ~50 instructions and ~450 cycles per trip, on
+// the headline's streams 7-10 trips for the slowest lane of a wave-word.  Measured (walkers alone, SQ counters per wave): 26 % fewer VALU
+// instructions but 13 % more wave-cycles than step32a on frame-like streams; 74 % fewer / 26 % fewer on silence.  It buys the demod
+// kernel beside it issue slots, not the walkers depth.
 // After the last walker a count/scan/pack pipeline, chunked on its own (finely), turns symbol bitmap + sign bitmap(s) into
 // bytes and the 1-based address of each byte's last symbol.  A slicer object's state (clock, last sign, open byte, address
 // count, differential state) enters and leaves through pm_slicer_state.
 #include "pm_common.h"
 #include "pm_slicer_step.inc"
+#include "pm_slicer_event.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -38,6 +43,12 @@ namespace {
 constexpr int kMaxJobs = 64;
 constexpr int kBlock = 256;     // four waves: one per SIMD when the grid is one workgroup per CU
 constexpr size_t kPinnedBytes = PM_PINNED_BYTES;
+// The event step (pm_slicer_event.h) for the full words of the walkers; -DPM_SLICER_EVENT=0 builds without it (A/B builds)
+#ifndef PM_SLICER_EVENT
+#define PM_SLICER_EVENT 1
+#endif
+constexpr int kEventCrossings = 24;   // a wave steps every sample of a word in which one of its lanes has more crossings than this
+constexpr double kEventMinSps = 16.0; // samples per symbol below which a batch keeps step32a (at most four symbols per word with events)
 constexpr int kShortLaunches = 10;    // launches of qwords words after the walkers' own chunks; 4 x qwords from then on
 
 struct JobDev {
@@ -186,14 +197,16 @@ __device__ __forceinline__ uint32_t step32a(double &clk, uint32_t zc, double tp,
 // means the words a walker touches were last written by an EARLIER launch and are touched by nobody else in this one.
 // A walker that reaches the end of its stream leaves the clock there as the stream's end state; walkers from further back
 // arrive in later launches and overwrite it, or merge before the end, in which case what stands there is already theirs.
-// STEP: 0 = step32 (compare and selects), 1 = step32m, 2 = step32m with zero low words in lock_rate - 1 and sps.  One kernel per
-// form: with the 64 unrolled steps of several forms in one kernel the loop no longer fits the instruction cache comfortably.
+// STEP: 0 = step32 (compare and selects), 1 = step32m, 2 = step32m with zero low words in lock_rate - 1 and sps, 3 / 4 = step32c,
+// 5 + LM0 + 2 NS0 = step32a, 9 + LM0 + 2 NS0 = the event step (pm_slicer_event.h) with step32a for the words in which some lane of
+// the wave has more than `evt` crossings (the wave runs as long as its slowest lane, and a lane's trips grow with its crossings).
+// One kernel per form: with the 64 unrolled steps of several forms in one kernel the loop no longer fits the instruction cache comfortably.
 template <int STEP>
 __global__ __launch_bounds__(kBlock) void slice_walk_kernel(const JobDev *__restrict__ jobs, int njobs, int lc_words, int qwords,
                                                         uint64_t *__restrict__ wclk, int32_t *__restrict__ wpos,
                                                         const int32_t *__restrict__ list_in, int32_t *__restrict__ list_out,
                                                         int *__restrict__ counts, int iter, uint64_t *__restrict__ symmap,
-                                                        uint64_t *__restrict__ ckmap, uint64_t *__restrict__ endstate, int prio)
+                                                        uint64_t *__restrict__ ckmap, uint64_t *__restrict__ endstate, int prio, int evt)
 {
     // These waves are bound by their own dependent chain; when FIR waves of another stream share the SIMD (pipelined executor)
     // every issue slot they lose lengthens the chain, while the FIR waves only need the slots in between: take issue priority.
@@ -229,6 +242,7 @@ __global__ __launch_bounds__(kBlock) void slice_walk_kernel(const JobDev *__rest
     if (quad) lq = w == 0 ? (uint64_t)lq0 : (bq[w - 1] >> 63);
     const double neg_sps = -sps;
     const double lm1 = lock - 1.0;
+    const double tpe = tp - kEventMargin;
     const gptr sm = (gptr)(symmap + word0);
     const gptr ck = (gptr)(ckmap + word0);
     bool alive = true;
@@ -276,9 +290,12 @@ __global__ __launch_bounds__(kBlock) void slice_walk_kernel(const JobDev *__rest
         asm volatile("" : : : "memory");
         const int64_t left = n - (w << 6);
         uint64_t sym;
-        if (left >= 64) {
+        if (STEP >= 9 && left >= 64 && !__ballot(__popcll(zc) > evt)) {     // 9 + LM0 + 2 NS0: events, the whole wave
+            int steps = 0;
+            sym = pm_event_word(clk, zc, tp, tpe, neg_sps, lm1, steps);
+        } else if (left >= 64) {
             uint32_t lo, hi;
-            if (STEP >= 5) {                       // 5 + LM0 + 2 NS0: the hand-scheduled form of step32c
+            if (STEP >= 5) {                // 5 + LM0 + 2 NS0: the hand-scheduled form of step32c
                 lo = step32a<((STEP - 5) & 1) != 0, ((STEP - 5) & 2) != 0>(clk, __brev((uint32_t)zc), tp, neg_sps, lm1);
                 hi = step32a<((STEP - 5) & 1) != 0, ((STEP - 5) & 2) != 0>(clk, __brev((uint32_t)(zc >> 32)), tp, neg_sps, lm1);
             } else if (STEP == 4) {
@@ -930,7 +947,13 @@ extern "C" int pm_slice_batch(pm_ctx *ctx, pm_slice_job *jobs, int njobs)
     bool direct = masks != 0 && !tn.slicer_mask_step;          // step32c: the decision from the clock itself
     for (const JobDev &d : jd) direct = direct && d.tp == d.tp;
     const bool hand = direct && !tn.slicer_compiled_step;
-    auto walk_kernel = hand ? (lm0 ? (ns0 ? slice_walk_kernel<8> : slice_walk_kernel<6>) : (ns0 ? slice_walk_kernel<7> : slice_walk_kernel<5>))
+    // the event step where every job of the batch meets its preconditions (pm_event_ok) and takes few enough symbols per word for it to
+    // pay (a trip costs ~7 samples of step32a; fsk_9600 at 5 samples per symbol ran its walkers twice as long), step32a otherwise
+    bool event = PM_SLICER_EVENT && hand && !tn.slicer_no_event_step;
+    for (const JobDev &d : jd) event = event && pm_event_ok(d.sps, d.lock, d.tp, d.clk0) && d.sps >= kEventMinSps;
+    const int evt = tn.slicer_event_crossings > 0 ? tn.slicer_event_crossings : kEventCrossings;
+    auto walk_kernel = event ? (lm0 ? (ns0 ? slice_walk_kernel<12> : slice_walk_kernel<10>) : (ns0 ? slice_walk_kernel<11> : slice_walk_kernel<9>))
+                       : hand ? (lm0 ? (ns0 ? slice_walk_kernel<8> : slice_walk_kernel<6>) : (ns0 ? slice_walk_kernel<7> : slice_walk_kernel<5>))
                        : direct ? (masks == 2 ? slice_walk_kernel<4> : slice_walk_kernel<3>)
                                 : masks == 2 ? slice_walk_kernel<2> : masks == 1 ? slice_walk_kernel<1> : slice_walk_kernel<0>;
     const unsigned wgrid = (unsigned)pm_cdiv(total_chunks, kBlock);
@@ -959,7 +982,7 @@ extern "C" int pm_slice_batch(pm_ctx *ctx, pm_slice_job *jobs, int njobs)
                 // the launch ends); the thin tail afterwards goes in longer launches: fewer dispatches, and few waves to waste
                 const int64_t qw = launches == 0 ? lc_words : launches <= kShortLaunches ? qwords : qtail;
                 hipLaunchKernelGGL(walk_kernel, dim3(wgrid), dim3(kBlock), 0, ctx->stream, d_jobs, nj, (int)lc_words, (int)qw, wclk, wpos,
-                                   lin, lout, counts, launches, symmap, ckmap, endstate, prio);
+                                   lin, lout, counts, launches, symmap, ckmap, endstate, prio, evt);
                 ++launches;
             }
         }
@@ -981,8 +1004,8 @@ extern "C" int pm_slice_batch(pm_ctx *ctx, pm_slice_job *jobs, int njobs)
         PM_HIP(hipGetLastError());
         const int alive = *h_last;
         if (trace) {
-            fprintf(stderr, "[slicer] chunk %lld words, %lld per launch, %lld walkers; alive after each of %d launches:", (long long)lc_words,
-                    (long long)qwords, (long long)total_chunks, launches);
+            fprintf(stderr, "[slicer] %s step, chunk %lld words, %lld per launch, %lld walkers; alive after each of %d launches:",
+                    event ? "event" : hand ? "step32a" : "compiled", (long long)lc_words, (long long)qwords, (long long)total_chunks, launches);
             for (size_t k = 1; k < ncopy; ++k) fprintf(stderr, " %d", h_counts[k]);
             fprintf(stderr, "\n");
         }
