@@ -36,7 +36,6 @@ struct pm_tuning {
     int lbatch_tail = -1;              // PM_LBATCH_TAIL: matched filters behind (0) or beside the next chunk's loops
     int agc_trace = 0;                 // PM_AGC_TRACE
     int slicer_max_chunk_words = 0, slicer_chunk_words = 0, slicer_quantum_words = 0;      // PM_SLICER_*_WORDS (0: the defaults)
-    int slicer_compare_step = 0, slicer_mask_step = 0, slicer_compiled_step = 0;           // older forms of the slicer step
     int slicer_trace = 0, slicer_no_setprio = 0;
     int slicer_no_event_step = 0, slicer_event_crossings = 0;                              // step32a everywhere / the event step's fallback threshold (0: default)
     int fir8 = 1;                      // PM_FIR8=0: the batch engine's matched filters in binary64 on the vector pipe

@@ -27,9 +27,6 @@ const TuneKey kTuneKeys[] = {
     {"slicer_max_chunk_words", "PM_SLICER_MAX_CHUNK_WORDS", &pm_tuning::slicer_max_chunk_words},
     {"slicer_chunk_words", "PM_SLICER_CHUNK_WORDS", &pm_tuning::slicer_chunk_words},
     {"slicer_quantum_words", "PM_SLICER_QUANTUM_WORDS", &pm_tuning::slicer_quantum_words},
-    {"slicer_compare_step", "PM_SLICER_COMPARE_STEP", &pm_tuning::slicer_compare_step},
-    {"slicer_mask_step", "PM_SLICER_MASK_STEP", &pm_tuning::slicer_mask_step},
-    {"slicer_compiled_step", "PM_SLICER_COMPILED_STEP", &pm_tuning::slicer_compiled_step},
     {"slicer_trace", "PM_SLICER_TRACE", &pm_tuning::slicer_trace}, {"slicer_no_setprio", "PM_SLICER_NO_SETPRIO", &pm_tuning::slicer_no_setprio},
     {"slicer_no_event_step", "PM_SLICER_NO_EVENT_STEP", &pm_tuning::slicer_no_event_step},
     {"slicer_event_crossings", "PM_SLICER_EVENT_CROSSINGS", &pm_tuning::slicer_event_crossings},

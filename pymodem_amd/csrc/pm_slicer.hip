@@ -21,7 +21,7 @@
 // walker reaching the end of its stream: sequential depth, never a wrong answer.
 //
 // A lone wave of step32a pays the loop-carried chain and the issue of 8 VALU instructions per sample: ~60 cycles per sample alone
-// (1.57 us per word on digital silence).  The event step (pm_slicer_event.h, STEP 9-12) steps only the samples at which the recurrence
+// (1.57 us per word on digital silence).  The event step (pm_slicer_event.h, SlicerForm::Event) steps only the samples at which the recurrence
 // does more than an exact clk += 1.0 and takes the runs between them as one addition: ~50 instructions and ~450 cycles per trip, on
 // the headline's streams 7-10 trips for the slowest lane of a wave-word.  Measured (walkers alone, SQ counters per wave): 26 % fewer VALU
 // instructions but 13 % more wave-cycles than step32a on frame-like streams; 74 % fewer / 26 % fewer on silence.  It buys the demod
@@ -48,7 +48,6 @@ constexpr size_t kPinnedBytes = PM_PINNED_BYTES;
 #define PM_SLICER_EVENT 1
 #endif
 constexpr int kEventCrossings = 24;   // a wave steps every sample of a word in which one of its lanes has more crossings than this
-constexpr double kEventMinSps = 16.0; // samples per symbol below which a batch keeps step32a (at most four symbols per word with events)
 constexpr int kShortLaunches = 10;    // launches of qwords words after the walkers' own chunks; 4 x qwords from then on
 
 struct JobDev {
@@ -57,7 +56,7 @@ struct JobDev {
     int64_t chunk0, nchunks;       // global chunk range of this stream
     int64_t word0;                 // offset of this stream in the global symbol bitmap
     double thr, sps, lock;
-    double tp;                     // the smallest clock for which fl(clk + 1.0) >= thr (step32c)
+    double tp;                     // the smallest clock for which fl(clk + 1.0) >= thr (step32a)
     int bps, mask, quad, pad;
     int demap[16];
     uint32_t *data32;
@@ -112,66 +111,22 @@ __device__ __forceinline__ uint32_t step32(double &clk, uint32_t zc, double thr,
     return sym;
 }
 
-// The same 32 steps with every decision kept in vector registers as a 0 / -1 mask (no compare-to-scalar round trip, fewer
-// instructions: a lone wave already takes most of its SIMD's issue slots, and these waves share SIMDs with FIR waves):
-//     nm   = sign bits of (a - thr) smeared: -1 where the symbol is NOT taken.  a >= thr  <=>  a - thr >= +0: the difference of
-//            two finite doubles is +0, never -0, when they are equal
-//     c    = a + (-sps & ~nm): a + (+0) is a itself (a is never -0: it is a sum with 1.0), a + (-sps) is slicer.py:81
-//     clk  = fma(c, lm1 & cm, c) with lm1 = lock_rate - 1 and cm = -1 on a crossing: c * (lock - 1) + c is c * lock in exact
-//            arithmetic when lock - 1 is exact (the host checks; Sterbenz for 0.5 <= lock <= 2), so the single rounding of the fma
-//            is the rounding of the reference's product (slicer.py:99-104); with a zero multiplier it returns c
-// The symbol flags are gathered as acc = 2 acc + nm; the word is acc - 1 - ... see the caller (sum of (1 + nm_k) 2^(31-k)).
+// The same 32 steps as hand-scheduled assembly (tools/gen_slicer_step.py -> pm_slicer_step.inc).  Per sample
+//     s   = clk >= tp                   the symbol decision taken from the clock itself: fl(clk + 1.0) >= thr  <=>  clk >= tp, where tp
+//                                       is the smallest double whose successor-by-one reaches thr (x -> fl(x + 1.0) is monotone, so the
+//                                       clocks that take a symbol are exactly [tp, inf); symbol_clock_threshold, pm_slicer_event.h)
+//     a   = clk + 1.0                   slicer.py:77
+//     c   = a + (s ? -sps : +0)         slicer.py:81; a + (+0) is a (a is never -0: it is a sum with 1.0)
+//     clk = fma(c, sel, c)              sel = lock_rate - 1 on a crossing, +0 otherwise: c * (lock - 1) + c is c * lock in exact
+//                                       arithmetic when lock - 1 is exact (the host checks; Sterbenz for 0.5 <= lock <= 2), so the single
+//                                       rounding of the fma is the rounding of the reference's product (slicer.py:99-104); with a zero
+//                                       multiplier it returns c
+// That takes the compare off the chain behind the addition: four dependent operations per sample instead of step32's six.  Written in
+// C++, the same operations cost 13 instructions per sample (the crossing mask as and + compare + select, a move to rebuild the
+// {0, -sps} pair, the symbol bit as select + shift + or); scheduled by hand they are 8 (10 when -sps and lock_rate - 1 have low words)
+// with the next sample's crossing mask prepared in the shadow of the chain compare -> select -> add -> fma.
 // LM0 / NS0: the low words of lock_rate - 1 / of sps are zero (0.75, 0.875, ...; every sps that is a small integer): one mask
 // operation less each.
-template <bool LM0, bool NS0>
-__device__ __forceinline__ uint32_t step32m(double &clk, uint32_t zc, double thr, double neg_sps, double lm1)
-{
-    const int32_t ns_hi = __double2hiint(neg_sps), ns_lo = __double2loint(neg_sps);
-    const int32_t lm_hi = __double2hiint(lm1), lm_lo = __double2loint(lm1);
-    uint32_t acc = 0;
-#pragma unroll
-    for (int k = 0; k < 32; ++k) {
-        const int32_t cm = (int32_t)(zc << k) >> 31;                     // crossing at this sample: -1
-        const double sel = __hiloint2double(lm_hi & cm, LM0 ? 0 : lm_lo & cm);
-        const double a = clk + 1.0;                                      // slicer.py:77
-        const int32_t nm = __double2hiint(a - thr) >> 31;                // slicer.py:79, negated
-        acc = (acc << 1) + (uint32_t)nm;
-        const double c = a + __hiloint2double(ns_hi & ~nm, NS0 ? 0 : ns_lo & ~nm);
-        clk = __builtin_fma(c, sel, c);
-    }
-    return acc - 1u;        // sum_k (1 + nm_k) 2^(31-k) = (2^32 - 1) + acc  (mod 2^32)
-}
-
-// The same 32 steps with the symbol decision taken from the clock itself: fl(clk + 1.0) >= thr  <=>  clk >= tp, where tp is the
-// smallest double whose successor-by-one reaches thr (x -> fl(x + 1.0) is monotone, so the clocks that take a symbol are exactly
-// [tp, inf); the host finds tp by stepping through the neighbours of thr - 1).  That takes the compare off the chain behind the
-// addition: compare | a = clk + 1.0 in parallel, then c = a + {0, -sps}, then the crossing's multiplication as one fma (see
-// step32m for why fma(c, lock - 1, c) is the reference's rounded product).  Four dependent operations per sample instead of six,
-// eight vector instructions instead of eleven: compare, select, two additions, fma, the symbol bit shifted in with the compare's
-// carry, and two for the crossing mask.
-template <bool LM0, bool NS0>
-__device__ __forceinline__ uint32_t step32c(double &clk, uint32_t zc, double tp, double neg_sps, double lm1)
-{
-    const int32_t ns_hi = __double2hiint(neg_sps), ns_lo = __double2loint(neg_sps);
-    const int32_t lm_hi = __double2hiint(lm1), lm_lo = __double2loint(lm1);
-    uint32_t acc = 0;
-#pragma unroll
-    for (int k = 0; k < 32; ++k) {
-        const int32_t cm = (int32_t)(zc << k) >> 31;                     // crossing at this sample: -1
-        const double sel = __hiloint2double(lm_hi & cm, LM0 ? 0 : lm_lo & cm);
-        const bool s = clk >= tp;                                        // slicer.py:77-79: (clk + 1.0) >= thr
-        const double a = clk + 1.0;                                      // slicer.py:77
-        acc = acc + acc + (s ? 1u : 0u);
-        const double c = a + __hiloint2double(s ? ns_hi : 0, NS0 ? 0 : (s ? ns_lo : 0));     // slicer.py:81; a + (+0) is a
-        clk = __builtin_fma(c, sel, c);                                  // slicer.py:99-104
-    }
-    return acc;
-}
-
-// step32c as hand-scheduled assembly (tools/gen_slicer_step.py -> pm_slicer_step.inc): the compiler's version of the same
-// source spends 13 instructions per sample (the crossing mask as and + compare + select, a move to rebuild the {0, -sps} pair,
-// the symbol bit as select + shift + or); scheduled by hand it is 8 (10 when -sps and lock_rate - 1 have low words) with the
-// next sample's crossing mask prepared in the shadow of the chain compare -> select -> add -> fma.
 template <bool LM0, bool NS0>
 __device__ __forceinline__ uint32_t step32a(double &clk, uint32_t zc, double tp, double neg_sps, double lm1)
 {
@@ -189,6 +144,51 @@ __device__ __forceinline__ uint32_t step32a(double &clk, uint32_t zc, double tp,
     return acc;
 }
 
+// What a word's steps read besides the clock and the crossings: the reference's operands (step32, the partial last word), step32a's,
+// and the event step's (SlicerForm::Event only).
+struct StepArgs {
+    double thr, sps, lock;
+    double tp, neg_sps, lm1;
+    double tpe;                    // fl(tp - kEventMargin)
+    int evt;                       // crossings in a lane's word above which its wave takes step32a for that word
+};
+
+// The steps of word w of a stream of n samples, for walkers and row slicers alike: the 64 of a full word (bit b of zc = sample b), or
+// the fewer of the stream's partial last word, which compares with thr as the reference does.  Returns the symbol flags in the same
+// orientation; clk is updated in place.  Event: the event step (pm_slicer_event.h) for the words in which no lane of the wave has more
+// than `evt` crossings (the wave runs as long as its slowest lane, and a lane's trips grow with its crossings), step32a for the others.
+template <SlicerForm F, bool LM0, bool NS0>
+__device__ __forceinline__ uint64_t slice_word(double &clk, uint64_t zc, int64_t n, int64_t w, const StepArgs &A)
+{
+    const int64_t left = n - (w << 6);
+    uint64_t sym;
+    if (F == SlicerForm::Event && left >= 64 && !__ballot(__popcll(zc) > A.evt)) {
+        int steps = 0;
+        sym = pm_event_word(clk, zc, A.tp, A.tpe, A.neg_sps, A.lm1, steps);
+    } else if (left >= 64) {
+        uint32_t lo, hi;
+        if (F == SlicerForm::Compare) {
+            lo = step32(clk, __brev((uint32_t)zc), A.thr, A.neg_sps, A.lock);
+            hi = step32(clk, __brev((uint32_t)(zc >> 32)), A.thr, A.neg_sps, A.lock);
+        } else {
+            lo = step32a<LM0, NS0>(clk, __brev((uint32_t)zc), A.tp, A.neg_sps, A.lm1);
+            hi = step32a<LM0, NS0>(clk, __brev((uint32_t)(zc >> 32)), A.tp, A.neg_sps, A.lm1);
+        }
+        sym = ((uint64_t)__brev(hi) << 32) | (uint64_t)__brev(lo);
+    } else {
+        sym = 0;
+        for (int b = 0; b < (int)left; ++b) {
+            clk += 1.0;
+            if (clk >= A.thr) {
+                clk -= A.sps;
+                sym |= 1ull << b;
+            }
+            if ((zc >> b) & 1) clk = clk * A.lock;
+        }
+    }
+    return sym;
+}
+
 // One lockstep launch of the walkers (see the header): every live walker advances by at most `qwords` words.  Work is a
 // dense list of walker (= chunk) ids; the first launch runs every walker through its own chunk (list_in == nullptr: identity)
 // and needs no comparison -- nobody has been there before.  Beyond its own chunk a walker compares, word by word, the clock it
@@ -197,11 +197,9 @@ __device__ __forceinline__ uint32_t step32a(double &clk, uint32_t zc, double tp,
 // means the words a walker touches were last written by an EARLIER launch and are touched by nobody else in this one.
 // A walker that reaches the end of its stream leaves the clock there as the stream's end state; walkers from further back
 // arrive in later launches and overwrite it, or merge before the end, in which case what stands there is already theirs.
-// STEP: 0 = step32 (compare and selects), 1 = step32m, 2 = step32m with zero low words in lock_rate - 1 and sps, 3 / 4 = step32c,
-// 5 + LM0 + 2 NS0 = step32a, 9 + LM0 + 2 NS0 = the event step (pm_slicer_event.h) with step32a for the words in which some lane of
-// the wave has more than `evt` crossings (the wave runs as long as its slowest lane, and a lane's trips grow with its crossings).
-// One kernel per form: with the 64 unrolled steps of several forms in one kernel the loop no longer fits the instruction cache comfortably.
-template <int STEP>
+// F, LM0, NS0: the step form (pm_slicer_choose, slice_word).  One kernel per form: with the 64 unrolled steps of several forms in one
+// kernel the loop no longer fits the instruction cache comfortably.
+template <SlicerForm F, bool LM0, bool NS0>
 __global__ __launch_bounds__(kBlock) void slice_walk_kernel(const JobDev *__restrict__ jobs, int njobs, int lc_words, int qwords,
                                                         uint64_t *__restrict__ wclk, int32_t *__restrict__ wpos,
                                                         const int32_t *__restrict__ list_in, int32_t *__restrict__ list_out,
@@ -240,9 +238,7 @@ __global__ __launch_bounds__(kBlock) void slice_walk_kernel(const JobDev *__rest
     uint64_t li = w == 0 ? (uint64_t)li0 : (bi[w - 1] >> 63);
     uint64_t lq = 1ull;
     if (quad) lq = w == 0 ? (uint64_t)lq0 : (bq[w - 1] >> 63);
-    const double neg_sps = -sps;
-    const double lm1 = lock - 1.0;
-    const double tpe = tp - kEventMargin;
+    const StepArgs A = {thr, sps, lock, tp, -sps, lock - 1.0, tp - kEventMargin, evt};
     const gptr sm = (gptr)(symmap + word0);
     const gptr ck = (gptr)(ckmap + word0);
     bool alive = true;
@@ -288,45 +284,7 @@ __global__ __launch_bounds__(kBlock) void slice_walk_kernel(const JobDev *__rest
         ck_n = __builtin_nontemporal_load(&ck[wn]);
         ck[w] = cb;
         asm volatile("" : : : "memory");
-        const int64_t left = n - (w << 6);
-        uint64_t sym;
-        if (STEP >= 9 && left >= 64 && !__ballot(__popcll(zc) > evt)) {     // 9 + LM0 + 2 NS0: events, the whole wave
-            int steps = 0;
-            sym = pm_event_word(clk, zc, tp, tpe, neg_sps, lm1, steps);
-        } else if (left >= 64) {
-            uint32_t lo, hi;
-            if (STEP >= 5) {                // 5 + LM0 + 2 NS0: the hand-scheduled form of step32c
-                lo = step32a<((STEP - 5) & 1) != 0, ((STEP - 5) & 2) != 0>(clk, __brev((uint32_t)zc), tp, neg_sps, lm1);
-                hi = step32a<((STEP - 5) & 1) != 0, ((STEP - 5) & 2) != 0>(clk, __brev((uint32_t)(zc >> 32)), tp, neg_sps, lm1);
-            } else if (STEP == 4) {
-                lo = step32c<true, true>(clk, __brev((uint32_t)zc), tp, neg_sps, lm1);
-                hi = step32c<true, true>(clk, __brev((uint32_t)(zc >> 32)), tp, neg_sps, lm1);
-            } else if (STEP == 3) {
-                lo = step32c<false, false>(clk, __brev((uint32_t)zc), tp, neg_sps, lm1);
-                hi = step32c<false, false>(clk, __brev((uint32_t)(zc >> 32)), tp, neg_sps, lm1);
-            } else if (STEP == 2) {
-                lo = step32m<true, true>(clk, __brev((uint32_t)zc), thr, neg_sps, lm1);
-                hi = step32m<true, true>(clk, __brev((uint32_t)(zc >> 32)), thr, neg_sps, lm1);
-            } else if (STEP == 1) {
-                lo = step32m<false, false>(clk, __brev((uint32_t)zc), thr, neg_sps, lm1);
-                hi = step32m<false, false>(clk, __brev((uint32_t)(zc >> 32)), thr, neg_sps, lm1);
-            } else {
-                lo = step32(clk, __brev((uint32_t)zc), thr, neg_sps, lock);
-                hi = step32(clk, __brev((uint32_t)(zc >> 32)), thr, neg_sps, lock);
-            }
-            sym = ((uint64_t)__brev(hi) << 32) | (uint64_t)__brev(lo);
-        } else {                                     // the stream's last, partial word
-            sym = 0;
-            for (int b = 0; b < (int)left; ++b) {
-                clk += 1.0;
-                if (clk >= thr) {
-                    clk -= sps;
-                    sym |= 1ull << b;
-                }
-                if ((zc >> b) & 1) clk = clk * lock;
-            }
-        }
-        sym_late = sym;
+        sym_late = slice_word<F, LM0, NS0>(clk, zc, n, w, A);
         late = true;
     }
     if (late) sm[w - 1] = sym_late;                  // the last word walked (a walker that retired had not stored it yet either)
@@ -612,27 +570,6 @@ __global__ void slice_init_kernel(const JobDev *__restrict__ jobs, int njobs, in
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-// The smallest double x with fl(x + 1.0) >= thr (NaN if it cannot be pinned down: the caller then keeps the compare on the sum).
-double symbol_clock_threshold(double thr)
-{
-    if (!(thr - thr == 0.0)) return NAN;
-    volatile double x = thr - 1.0;
-    for (int k = 0; k < 64; ++k) {                       // down while the predecessor still reaches thr
-        volatile double p = nextafter((double)x, -INFINITY);
-        volatile double sum = p + 1.0;
-        if (!(sum >= thr)) break;
-        x = p;
-        if (k == 63) return NAN;
-    }
-    for (int k = 0; k < 64; ++k) {                       // up until it does
-        volatile double sum = x + 1.0;
-        if (sum >= thr) return x;
-        x = nextafter((double)x, INFINITY);
-    }
-    return NAN;
-}
-
-
 // ---- one lane per stream, a chunk of the stream per launch (the carrier-loop batch engine, pm_loopbatch.hip) -------------------------
 // The engine advances thousands of streams together, a time chunk at a time, and its loops are sequential in exactly the way the
 // slicer's clock is: here the parallelism is across the streams, so every stream gets ONE lane that carries the true state from chunk
@@ -647,7 +584,7 @@ struct RowParams {
     unsigned long long demap4;       // demap[16], four bits each
 };
 
-template <int STEP>
+template <SlicerForm F, bool LM0, bool NS0>
 __global__ __launch_bounds__(64) void rowslice_kernel(const RowParams *__restrict__ params, int chains, int rows, int quad,
                                                       const uint64_t *__restrict__ bits_i, const uint64_t *__restrict__ bits_q, int64_t stride,
                                                       int64_t first, int64_t count, pm_rowslice_rec *__restrict__ recs,
@@ -660,7 +597,7 @@ __global__ __launch_bounds__(64) void rowslice_kernel(const RowParams *__restric
     pm_rowslice_rec R = recs[row];
     const gptr_c bi = (gptr_c)(bits_i + (int64_t)row * stride);
     const gptr_c bq = quad ? (gptr_c)(bits_q + (int64_t)row * stride) : bi;
-    const double thr = P.thr, sps = P.sps, lock = P.lock, tp = P.tp, neg_sps = -P.sps, lm1 = P.lock - 1.0;
+    const StepArgs A = {P.thr, P.sps, P.lock, P.tp, -P.sps, P.lock - 1.0, 0.0, 0};      // (no event step here)
     const int bps = P.bps;
     const uint32_t mask = (uint32_t)P.mask;
     const unsigned long long demap4 = P.demap4;
@@ -685,44 +622,10 @@ __global__ __launch_bounds__(64) void rowslice_kernel(const RowParams *__restric
         uint64_t zc = si ^ ((si << 1) | li);
         if (quad) zc |= sq ^ ((sq << 1) | lq);
         const int64_t left = count - (w << 6);
-        uint64_t sym;
-        if (left >= 64) {
-            li = si >> 63;
-            lq = sq >> 63;
-            uint32_t lo, hi;
-            if (STEP >= 5) {
-                lo = step32a<((STEP - 5) & 1) != 0, ((STEP - 5) & 2) != 0>(clk, __brev((uint32_t)zc), tp, neg_sps, lm1);
-                hi = step32a<((STEP - 5) & 1) != 0, ((STEP - 5) & 2) != 0>(clk, __brev((uint32_t)(zc >> 32)), tp, neg_sps, lm1);
-            } else if (STEP == 4) {
-                lo = step32c<true, true>(clk, __brev((uint32_t)zc), tp, neg_sps, lm1);
-                hi = step32c<true, true>(clk, __brev((uint32_t)(zc >> 32)), tp, neg_sps, lm1);
-            } else if (STEP == 3) {
-                lo = step32c<false, false>(clk, __brev((uint32_t)zc), tp, neg_sps, lm1);
-                hi = step32c<false, false>(clk, __brev((uint32_t)(zc >> 32)), tp, neg_sps, lm1);
-            } else if (STEP == 2) {
-                lo = step32m<true, true>(clk, __brev((uint32_t)zc), thr, neg_sps, lm1);
-                hi = step32m<true, true>(clk, __brev((uint32_t)(zc >> 32)), thr, neg_sps, lm1);
-            } else if (STEP == 1) {
-                lo = step32m<false, false>(clk, __brev((uint32_t)zc), thr, neg_sps, lm1);
-                hi = step32m<false, false>(clk, __brev((uint32_t)(zc >> 32)), thr, neg_sps, lm1);
-            } else {
-                lo = step32(clk, __brev((uint32_t)zc), thr, neg_sps, lock);
-                hi = step32(clk, __brev((uint32_t)(zc >> 32)), thr, neg_sps, lock);
-            }
-            sym = ((uint64_t)__brev(hi) << 32) | (uint64_t)__brev(lo);
-        } else {                                             // the stream's last, partial word (bits past the end are not samples)
-            li = (si >> (left - 1)) & 1;
-            lq = (sq >> (left - 1)) & 1;
-            sym = 0;
-            for (int b = 0; b < (int)left; ++b) {
-                clk += 1.0;
-                if (clk >= thr) {
-                    clk -= sps;
-                    sym |= 1ull << b;
-                }
-                if ((zc >> b) & 1) clk = clk * lock;
-            }
-        }
+        const int last = left >= 64 ? 63 : (int)left - 1;   // the word's last sample (in the partial last word the bits past it are not samples)
+        li = (si >> last) & 1;
+        lq = (sq >> last) & 1;
+        uint64_t sym = slice_word<F, LM0, NS0>(clk, zc, count, w, A);
         while (sym) {
             const int b = __ffsll((long long)sym) - 1;
             sym &= sym - 1;
@@ -796,6 +699,18 @@ __global__ __launch_bounds__(256) void rows_gather_kernel(const pm_rowslice_rec 
     for (unsigned long long i = t; i < sw; i += 256) dst[i] = src_s[i];
     for (unsigned long long i = t; i < dw; i += 256) dst[sw + i] = src_d[i];
 }
+
+// The kernels of a form, by form_index: Compare, then Hand and Event with LM0 + 2 NS0 each.
+constexpr SlicerForm kC = SlicerForm::Compare, kH = SlicerForm::Hand, kE = SlicerForm::Event;
+const char *const kFormNames[] = {"compare", "step32a", "event"};      // the [slicer] trace's name of a form
+int form_index(SlicerStep f) { return f.form == kC ? 0 : (f.form == kE ? 5 : 1) + f.lm0 + 2 * f.ns0; }
+decltype(&slice_walk_kernel<kC, false, false>) const kWalkKernels[] = {
+    slice_walk_kernel<kC, false, false>,
+    slice_walk_kernel<kH, false, false>, slice_walk_kernel<kH, true, false>, slice_walk_kernel<kH, false, true>, slice_walk_kernel<kH, true, true>,
+    slice_walk_kernel<kE, false, false>, slice_walk_kernel<kE, true, false>, slice_walk_kernel<kE, false, true>, slice_walk_kernel<kE, true, true>};
+decltype(&rowslice_kernel<kC, false, false>) const kRowKernels[] = {      // (no Event: the row slicers are chosen without it)
+    rowslice_kernel<kC, false, false>,
+    rowslice_kernel<kH, false, false>, rowslice_kernel<kH, true, false>, rowslice_kernel<kH, false, true>, rowslice_kernel<kH, true, true>};
 
 }  // namespace
 
@@ -930,32 +845,11 @@ extern "C" int pm_slice_batch(pm_ctx *ctx, pm_slice_job *jobs, int njobs)
     hipLaunchKernelGGL(slice_init_kernel, dim3((unsigned)std::min<int64_t>(pm_cdiv(std::max<int64_t>(total_chunks, ncounts), kBlock), 1024)),
                        dim3(kBlock), 0, ctx->stream, d_jobs, nj, (int)lc_words, total_chunks, wclk, wpos, counts, ncounts, tails);
 
-    // step32m needs lock_rate - 1 to be exact for every stream of the batch (it is for 0.5 <= lock_rate <= 2) and finite clocks
-    int masks = tn.slicer_compare_step ? 0 : 2;
-    bool lm0 = true, ns0 = true;                     // low words of lock_rate - 1 / of sps zero in every stream
-    for (const JobDev &d : jd) {
-        const volatile double lm1 = d.lock - 1.0;
-        if (!(lm1 + 1.0 == d.lock) || !(d.clk0 - d.clk0 == 0.0) || !(d.sps - d.sps == 0.0)) masks = 0;
-        uint64_t lb, sb;
-        const double l1 = lm1;
-        memcpy(&lb, &l1, 8);
-        memcpy(&sb, &d.sps, 8);
-        if (masks == 2 && ((uint32_t)lb || (uint32_t)sb)) masks = 1;     // low words not zero: the general mask form
-        lm0 = lm0 && (uint32_t)lb == 0;
-        ns0 = ns0 && (uint32_t)sb == 0;
-    }
-    bool direct = masks != 0 && !tn.slicer_mask_step;          // step32c: the decision from the clock itself
-    for (const JobDev &d : jd) direct = direct && d.tp == d.tp;
-    const bool hand = direct && !tn.slicer_compiled_step;
-    // the event step where every job of the batch meets its preconditions (pm_event_ok) and takes few enough symbols per word for it to
-    // pay (a trip costs ~7 samples of step32a; fsk_9600 at 5 samples per symbol ran its walkers twice as long), step32a otherwise
-    bool event = PM_SLICER_EVENT && hand && !tn.slicer_no_event_step;
-    for (const JobDev &d : jd) event = event && pm_event_ok(d.sps, d.lock, d.tp, d.clk0) && d.sps >= kEventMinSps;
+    std::vector<SlicerJob> sj;
+    for (const JobDev &d : jd) sj.push_back({d.sps, d.lock, d.tp, d.clk0});
+    const SlicerStep form = pm_slicer_choose(sj.data(), nj, PM_SLICER_EVENT && !tn.slicer_no_event_step);
     const int evt = tn.slicer_event_crossings > 0 ? tn.slicer_event_crossings : kEventCrossings;
-    auto walk_kernel = event ? (lm0 ? (ns0 ? slice_walk_kernel<12> : slice_walk_kernel<10>) : (ns0 ? slice_walk_kernel<11> : slice_walk_kernel<9>))
-                       : hand ? (lm0 ? (ns0 ? slice_walk_kernel<8> : slice_walk_kernel<6>) : (ns0 ? slice_walk_kernel<7> : slice_walk_kernel<5>))
-                       : direct ? (masks == 2 ? slice_walk_kernel<4> : slice_walk_kernel<3>)
-                                : masks == 2 ? slice_walk_kernel<2> : masks == 1 ? slice_walk_kernel<1> : slice_walk_kernel<0>;
+    const auto walk_kernel = kWalkKernels[form_index(form)];
     const unsigned wgrid = (unsigned)pm_cdiv(total_chunks, kBlock);
     const bool trace = tn.slicer_trace != 0;
     const int prio = tn.slicer_no_setprio ? 0 : 1;
@@ -1004,8 +898,8 @@ extern "C" int pm_slice_batch(pm_ctx *ctx, pm_slice_job *jobs, int njobs)
         PM_HIP(hipGetLastError());
         const int alive = *h_last;
         if (trace) {
-            fprintf(stderr, "[slicer] %s step, chunk %lld words, %lld per launch, %lld walkers; alive after each of %d launches:",
-                    event ? "event" : hand ? "step32a" : "compiled", (long long)lc_words, (long long)qwords, (long long)total_chunks, launches);
+            fprintf(stderr, "[slicer] %s step (LM0 %d, NS0 %d), chunk %lld words, %lld per launch, %lld walkers; alive after each of %d launches:",
+                    kFormNames[(int)form.form], form.lm0, form.ns0, (long long)lc_words, (long long)qwords, (long long)total_chunks, launches);
             for (size_t k = 1; k < ncopy; ++k) fprintf(stderr, " %d", h_counts[k]);
             fprintf(stderr, "\n");
         }
@@ -1191,7 +1085,8 @@ int pm_slicer_stats(pm_ctx *ctx, int32_t *iterations, int32_t *chunk_len, int64_
 
 // ---- the batch engine's row slicers (rowslice_kernel) ----------------------------------------------------------------------------
 struct pm_rowslice {
-    int chains = 0, step = 0, device = 0;
+    int chains = 0, device = 0;
+    SlicerStep form{};
     RowParams *d_params = nullptr;
     std::vector<pm_slicer_params> made_for;
 };
@@ -1202,9 +1097,7 @@ int pm_rowslice_create(pm_ctx *ctx, const pm_slicer_params *h_params, int chains
     PM_ARG(h_params != nullptr && out != nullptr && chains >= 1 && chains <= 4096);
     *out = nullptr;
     std::vector<RowParams> rp((size_t)chains);
-    const pm_tuning &tn = ctx->tune;
-    int masks = tn.slicer_compare_step ? 0 : 2;              // the choice of pm_slice_batch, over the chains' parameter sets
-    bool lm0 = true, ns0 = true, direct = true;
+    std::vector<SlicerJob> sj((size_t)chains);
     for (int c = 0; c < chains; ++c) {
         const pm_slicer_params &q = h_params[c];
         PM_ARG(q.bits_per_symbol == 1 || q.bits_per_symbol == 2);
@@ -1221,23 +1114,12 @@ int pm_rowslice_create(pm_ctx *ctx, const pm_slicer_params *h_params, int chains
             PM_ARG(q.demap[i] >= 0 && q.demap[i] < (1 << q.bits_per_symbol));
             d.demap4 |= (unsigned long long)q.demap[i] << (4 * i);
         }
-        const volatile double lm1 = d.lock - 1.0;
-        if (!(lm1 + 1.0 == d.lock) || !(d.sps - d.sps == 0.0)) masks = 0;
-        uint64_t lb, sb;
-        const double l1 = lm1;
-        memcpy(&lb, &l1, 8);
-        memcpy(&sb, &d.sps, 8);
-        if (masks == 2 && ((uint32_t)lb || (uint32_t)sb)) masks = 1;
-        lm0 = lm0 && (uint32_t)lb == 0;
-        ns0 = ns0 && (uint32_t)sb == 0;
-        direct = direct && d.tp == d.tp;
+        sj[(size_t)c] = {d.sps, d.lock, d.tp, 0.0};          // (the row slicers do not look at the clock they start from)
     }
-    direct = direct && masks != 0 && !tn.slicer_mask_step;
-    const bool hand = direct && !tn.slicer_compiled_step;
     pm_rowslice *rs = new pm_rowslice();
     rs->chains = chains;
     rs->device = ctx->device;
-    rs->step = hand ? (lm0 ? (ns0 ? 8 : 6) : (ns0 ? 7 : 5)) : direct ? (masks == 2 ? 4 : 3) : masks;
+    rs->form = pm_slicer_choose(sj.data(), chains, false);  // no event step in the row slicers
     rs->made_for.assign(h_params, h_params + chains);
     if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc((void **)&rs->d_params, sizeof(RowParams) * (size_t)chains) != hipSuccess) {
         delete rs;
@@ -1272,20 +1154,8 @@ int pm_rowslice_chunk(pm_ctx *ctx, const pm_rowslice *rs, int rows, int quad, co
     PM_ARG(first >= 0 && first % 64 == 0 && count >= 1 && stride >= (count + 63) / 64 && cap >= 8 && cap % 8 == 0 && rs->device == ctx->device);
     PmProf prof(ctx, PM_K_SLICE_ITER);
     const dim3 grid((unsigned)pm_cdiv(rows, 64)), block(64);
-#define PM_ROWSLICE(S) hipLaunchKernelGGL(rowslice_kernel<S>, grid, block, 0, ctx->stream, rs->d_params, rs->chains, rows, quad, d_bi, d_bq, stride, first, count, \
-                                          d_recs, d_data, d_steps, cap)
-    switch (rs->step) {
-    case 8: PM_ROWSLICE(8); break;
-    case 7: PM_ROWSLICE(7); break;
-    case 6: PM_ROWSLICE(6); break;
-    case 5: PM_ROWSLICE(5); break;
-    case 4: PM_ROWSLICE(4); break;
-    case 3: PM_ROWSLICE(3); break;
-    case 2: PM_ROWSLICE(2); break;
-    case 1: PM_ROWSLICE(1); break;
-    default: PM_ROWSLICE(0); break;
-    }
-#undef PM_ROWSLICE
+    hipLaunchKernelGGL(kRowKernels[form_index(rs->form)], grid, block, 0, ctx->stream, rs->d_params, rs->chains, rows, quad, d_bi, d_bq, stride, first,
+                       count, d_recs, d_data, d_steps, cap);
     PM_HIP(hipGetLastError());
     return PM_OK;
 }

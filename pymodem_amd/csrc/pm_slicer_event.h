@@ -1,8 +1,10 @@
-// The slicer's event step (slice_walk_kernel, STEP 9-12): the samples of a word at which the reference recurrence does anything but
-// an exact clk += 1.0, found ahead of time, and the runs between them taken as one addition.  Plain C++ so that the host model
-// (tests/slicer_event_model.cpp) runs the very code the kernel runs.
+// The slicer's event step (slice_walk_kernel<SlicerForm::Event, ...>): the samples of a word at which the reference recurrence does
+// anything but an exact clk += 1.0, found ahead of time, and the runs between them taken as one addition; and the host's choice of a
+// batch's step form (pm_slicer_choose).  Plain C++ so that the host model (tests/slicer_event_model.cpp) runs the very code the kernel
+// and its launchers run.
 //
-// Per sample the walker executes (step32c): s = clk >= tp;  a = clk + 1.0;  c = a + (s ? -sps : +0);  clk = fma(c, crossing ? lock - 1 : +0, c).
+// Per sample the walker executes (step32a in pm_slicer.hip, which says why each operation is the reference's own):
+//     s = clk >= tp;  a = clk + 1.0;  c = a + (s ? -sps : +0);  clk = fma(c, crossing ? lock - 1 : +0, c).
 // A sample is an EVENT if it is a crossing, or takes a symbol (clk >= tp), or its addition rounds (fl(clk + 1.0) != clk + 1.0).
 // Every other sample leaves clk + 1.0 exactly (c = a + (+0) = a, fma(a, +0, a) = a), so a run of k of them is clk + k, and when
 // every clk + j (0 <= j <= k) is a double, the one addition fl(clk + k) is that value too: bit for bit the k steps.
@@ -95,10 +97,62 @@ PM_EVENT_HD uint64_t pm_event_word(double &clk, uint64_t zc, double tp, double t
         const bool s = clk >= tp;                                  // slicer.py:77-79
         const double a = clk + 1.0;                                // slicer.py:77
         const double c = a + (s ? neg_sps : 0.0);                  // slicer.py:81
-        clk = fma(c, ((zc >> q) & 1) ? lm1 : 0.0, c);              // slicer.py:99-104 (step32m: the rounded product clk * lock)
+        clk = fma(c, ((zc >> q) & 1) ? lm1 : 0.0, c);              // slicer.py:99-104 (step32a: the rounded product clk * lock)
         sym |= (uint64_t)s << q;
         zm = zc & (~1ull << q);
         p = q + 1;
     }
     return sym;
+}
+
+// The smallest double x with fl(x + 1.0) >= thr (NaN if it cannot be pinned down: the batch then keeps the compare on the sum).
+inline double symbol_clock_threshold(double thr)
+{
+    if (!(thr - thr == 0.0)) return NAN;
+    volatile double x = thr - 1.0;
+    for (int k = 0; k < 64; ++k) {                       // down while the predecessor still reaches thr
+        volatile double p = nextafter((double)x, -INFINITY);
+        volatile double sum = p + 1.0;
+        if (!(sum >= thr)) break;
+        x = p;
+        if (k == 63) return NAN;
+    }
+    for (int k = 0; k < 64; ++k) {                       // up until it does
+        volatile double sum = x + 1.0;
+        if (sum >= thr) return x;
+        x = nextafter((double)x, INFINITY);
+    }
+    return NAN;
+}
+
+// The forms of a word's 64 steps (pm_slicer.hip): Compare = step32, the reference's compare and select, for any parameters;
+// Hand = step32a, the decision read off the clock and the crossing's product as an fma; Event = the event step above, with step32a
+// for the words in which some lane of the wave has too many crossings (walkers only).  LM0 / NS0: the low words of lock_rate - 1 /
+// of sps are zero in every job (step32a saves an instruction per sample on each).
+enum class SlicerForm { Compare, Hand, Event };
+struct SlicerStep {
+    SlicerForm form;
+    bool lm0, ns0;
+};
+struct SlicerJob {
+    double sps, lock, tp, clk0;
+};
+constexpr double kEventMinSps = 16.0;   // samples per symbol below which a batch keeps step32a (at most four symbols per word with events)
+
+// One form for a whole batch.  Hand needs lock_rate - 1 exact (the fma form; it is for 0.5 <= lock_rate <= 2) and finite sps, clk0
+// and tp; Event on top of it, where `event` allows it, every job meets pm_event_ok and takes few enough symbols per word for it to pay
+// (a trip costs ~7 samples of step32a; fsk_9600 at 5 samples per symbol ran its walkers twice as long).
+inline SlicerStep pm_slicer_choose(const SlicerJob *jobs, int njobs, bool event)
+{
+    bool hand = true, lm0 = true, ns0 = true;
+    for (int j = 0; j < njobs; ++j) {
+        const SlicerJob &d = jobs[j];
+        const volatile double lm1 = d.lock - 1.0;
+        hand = hand && lm1 + 1.0 == d.lock && d.sps - d.sps == 0.0 && d.clk0 - d.clk0 == 0.0 && d.tp - d.tp == 0.0;
+        lm0 = lm0 && (uint32_t)pm_event_bits(lm1) == 0;
+        ns0 = ns0 && (uint32_t)pm_event_bits(d.sps) == 0;
+        event = event && pm_event_ok(d.sps, d.lock, d.tp, d.clk0) && d.sps >= kEventMinSps;
+    }
+    if (!hand) return {SlicerForm::Compare, false, false};
+    return {event ? SlicerForm::Event : SlicerForm::Hand, lm0, ns0};
 }

@@ -1,5 +1,6 @@
 // Host model of the slicer walkers' event step (tests/test_slicer_event_model.py): the kernel's own pm_slicer_event.h, compiled for the
-// CPU, beside the reference recurrence (slicer.py:59-107) sample by sample.  Built as a shared library and driven through ctypes.
+// CPU, beside the reference recurrence (slicer.py:59-107) sample by sample, and the launchers' choice of step form.  Built as a shared
+// library and driven through ctypes.
 #include "../pymodem_amd/csrc/pm_slicer_event.h"
 #include <cstdint>
 
@@ -8,6 +9,18 @@ extern "C" {
 int model_ok(double sps, double lock, double tp, double clk0) { return pm_event_ok(sps, lock, tp, clk0) ? 1 : 0; }
 
 int model_run(double clk, double tpe) { return pm_event_run(clk, tpe); }
+
+double model_threshold(double thr) { return symbol_clock_threshold(thr); }
+
+// pm_slicer_choose over njobs jobs (tp from the header's symbol_clock_threshold, as the launchers take it): form * 4 + lm0 + 2 ns0
+int model_choose(const double *sps, const double *lock, const double *clk0, int njobs, int event)
+{
+    SlicerJob jobs[64];
+    if (njobs < 1 || njobs > 64) return -1;
+    for (int j = 0; j < njobs; ++j) jobs[j] = {sps[j], lock[j], symbol_clock_threshold(sps[j] / 2.0 - 0.5), clk0[j]};
+    const SlicerStep f = pm_slicer_choose(jobs, njobs, event != 0);
+    return (int)f.form * 4 + (f.lm0 ? 1 : 0) + (f.ns0 ? 2 : 0);
+}
 
 // The reference: per sample clk += 1.0; clk >= thr takes a symbol and clk -= sps; a crossing multiplies by lock_rate.
 // zc: crossing flags, bit b of word w = sample 64 w + b.  ck[w] = the clock entering word w, sym[w] = its symbol flags.
@@ -29,7 +42,7 @@ double model_plain(double clk, const uint64_t *zc, int64_t nwords, double thr, d
     return clk;
 }
 
-// The walker's full words: the event step, or -- in a word with more than `evt` crossings -- step32c's operations sample by sample
+// The walker's full words: the event step, or -- in a word with more than `evt` crossings -- step32a's operations sample by sample
 // (the kernel's wave-uniform fallback, seen from one lane).  `events` counts the real steps the event form took.
 double model_event(double clk, const uint64_t *zc, int64_t nwords, double tp, double sps, double lock, int evt, uint64_t *sym, double *ck,
                    int64_t *events)

@@ -302,6 +302,42 @@ def test_quadrature_slicer_bit_exact(ctx, rate, cfg, lock, kind):
         assert np.array_equal(got.data, d) and np.array_equal(got.address, a), (n, kind, s.last_stats)
 
 
+@pytest.mark.parametrize("kind", ["noise", "smooth"])
+@pytest.mark.parametrize("rate,cfg", [(48000, "1200"), (8000, "300"), (48000, "9600")])
+def test_binary_slicer_compare_step_bit_exact(ctx, rate, cfg, kind, capfd):
+    """lock_rate 0.45: lock_rate - 1 is not exact, so the walkers take the reference's compare and select (SlicerForm::Compare)."""
+    from pymodem_amd.slicer import BinarySlicer
+    for n in [1, 100, 1025, 40000, 300001]:
+        x = slicer_input(n, n + rate, kind)
+        s = BinarySlicer(sample_rate=rate, config=cfg)
+        s.StringOptionsRetune({"lock_rate": "0.45"})
+        with tuned(ctx, slicer_trace=1):
+            got = s.slice(x)
+        d, a = O.BinarySlicer(rate, cfg, {"lock_rate": "0.45"}).slice(x)
+        assert np.array_equal(got.data, d) and np.array_equal(got.address, a), (n, kind, s.last_stats)
+    forms = {l.split()[1] for l in capfd.readouterr().err.splitlines() if l.startswith("[slicer] ")}
+    assert forms == {"compare"}, forms
+
+
+@pytest.mark.parametrize("kind", ["noise", "smooth"])
+@pytest.mark.parametrize("rate,cfg", [(48000, "qpsk_2400"), (8000, "qpsk_600"), (48000, "bpsk_300")])
+def test_quadrature_slicer_compare_step_bit_exact(ctx, rate, cfg, kind, capfd):
+    from pymodem_amd.data_classes import IQData
+    from pymodem_amd.slicer import QuadratureSlicer
+    for n in [1, 777, 4096, 50001, 300000]:
+        iq = IQData()
+        iq.i_data = slicer_input(n, n + rate, kind)
+        iq.q_data = slicer_input(n, n + rate + 1, kind)
+        s = QuadratureSlicer(sample_rate=rate, config=cfg)
+        s.StringOptionsRetune({"lock_rate": "0.45"})
+        with tuned(ctx, slicer_trace=1):
+            got = s.slice(iq)
+        d, a = O.QuadratureSlicer(rate, cfg, {"lock_rate": "0.45"}).slice((iq.i_data, iq.q_data))
+        assert np.array_equal(got.data, d) and np.array_equal(got.address, a), (n, kind, s.last_stats)
+    forms = {l.split()[1] for l in capfd.readouterr().err.splitlines() if l.startswith("[slicer] ")}
+    assert forms == {"compare"}, forms
+
+
 @pytest.mark.parametrize("kind", ["noise", "smooth", "alternating"])
 def test_slicers_continue_across_calls(ctx, kind):
     """A slicer object carries phase clock, last sample sign, the open byte and the address count from one slice() to the next

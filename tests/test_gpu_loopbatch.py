@@ -328,6 +328,19 @@ def test_sliced_run_equals_run_then_slice_batch(cfg, rate, carriers, chunk, n):
     engine's bitmaps sliced by pm_slice_batch (itself pinned to the oracle's slicers in tests/test_gpu_slicer.py): bytes, addresses and
     the slicer objects' end states, for binary and quadrature slicers, several chunks and a ragged last word, noise (a crossing
     at nearly every sample) and level steps."""
+    sliced_run_vs_slice_batch(cfg, rate, carriers, chunk, n)
+
+
+@pytest.mark.parametrize("cfg,rate,carriers,chunk,n", [
+    ("bpsk_300.json", 48000, [1490.0, 1500.0, 1512.5], 4096, 41234),
+    ("qpsk_2400.json", 48000, [1500.0 + 3.125 * k for k in range(-4, 4)], 6144, 30001),
+])
+def test_sliced_run_equals_run_then_slice_batch_compare_step(cfg, rate, carriers, chunk, n):
+    """The same at lock_rate 0.45 (lock_rate - 1 not exact): both sides on the reference's compare and select (SlicerForm::Compare)."""
+    sliced_run_vs_slice_batch(cfg, rate, carriers, chunk, n, lock="0.45")
+
+
+def sliced_run_vs_slice_batch(cfg, rate, carriers, chunk, n, lock=None):
     import pymodem_amd
     from pymodem_amd import chain_builder as cb
     from pymodem_amd.loop_batch import LoopBatch
@@ -340,7 +353,11 @@ def test_sliced_run_equals_run_then_slice_batch(cfg, rate, carriers, chunk, n):
     t = np.arange(n)
     recs[2] = (6000 * np.sin(2 * np.pi * 1500.0 * t / rate) * np.sign(np.sin(2 * np.pi * 37.0 * t / rate))).astype(np.int16)      # a keyed carrier
     def slicers():
-        return [cb.build_chain(rate, line)[2] for line, _ in group]
+        out = [cb.build_chain(rate, line)[2] for line, _ in group]
+        if lock is not None:
+            for sl in out:
+                sl.StringOptionsRetune({"lock_rate": lock})
+        return out
     eng = LoopBatch(modems, recordings=5, ctx=ctx, chunk=chunk)
     try:
         dev = [ctx.upload(r) for r in recs]

@@ -1,7 +1,8 @@
-"""The walkers' event step (slice_walk_kernel STEP 9-12, pymodem_amd/csrc/pm_slicer_event.h) against the step it replaces (step32a,
-switch slicer_no_event_step): every slicer byte, its stream address and the end state the slicer object carries to its next call,
-bit for bit -- on the headline's recording through the pipeline bench.py times, on noise, on silence, on band-limited streams, and
-with the wave-uniform fallback threshold (slicer_event_crossings) on both sides of the streams' crossing counts."""
+"""The walkers' event step (slice_walk_kernel<SlicerForm::Event, ...>, pymodem_amd/csrc/pm_slicer_event.h) against the step it
+replaces (SlicerForm::Hand, step32a; switch slicer_no_event_step): every slicer byte, its stream address and the end state the slicer
+object carries to its next call, bit for bit -- on the headline's recording through the pipeline bench.py times, on noise, on silence,
+on band-limited streams, and with the wave-uniform fallback threshold (slicer_event_crossings) on both sides of the streams' crossing
+counts."""
 import os
 import subprocess
 import sys

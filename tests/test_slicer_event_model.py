@@ -28,11 +28,13 @@ def model(tmp_path_factory):
     lib.model_run.argtypes, lib.model_run.restype = [_d, _d], _i
     lib.model_plain.argtypes, lib.model_plain.restype = [_d, _vp, _i64, _d, _d, _d, _vp, _vp], _d
     lib.model_event.argtypes, lib.model_event.restype = [_d, _vp, _i64, _d, _d, _d, _i, _vp, _vp, _vp], _d
+    lib.model_threshold.argtypes, lib.model_threshold.restype = [_d], _d
+    lib.model_choose.argtypes, lib.model_choose.restype = [_vp, _vp, _vp, _i, _i], _i
     return lib
 
 
 def symbol_clock_threshold(thr):
-    """pm_slicer.hip symbol_clock_threshold: the smallest double x with fl(x + 1.0) >= thr."""
+    """pm_slicer_event.h symbol_clock_threshold: the smallest double x with fl(x + 1.0) >= thr."""
     x = thr - 1.0
     while math.nextafter(x, -math.inf) + 1.0 >= thr:
         x = math.nextafter(x, -math.inf)
@@ -183,3 +185,56 @@ def test_host_precondition_rejects_what_the_bound_does_not_cover(model):
                                (40.0, 0.77, tp, math.nan), (40.0, 0.77, tp, math.inf), (math.inf, 0.77, tp, 0.0)]:
         assert not model.model_ok(sps, lock, t, clk0), (sps, lock, t, clk0)
 
+
+
+COMPARE, HAND, EVENT = 0, 1, 2          # SlicerForm
+
+
+def choose(model, jobs, event=True):
+    """pm_slicer_choose over jobs of (sps, lock, clk0): (form, lm0, ns0)."""
+    sps, lock, clk0 = (np.ascontiguousarray([j[k] for j in jobs], np.float64) for k in range(3))
+    r = model.model_choose(sps.ctypes.data, lock.ctypes.data, clk0.ctypes.data, len(jobs), int(event))
+    assert r >= 0
+    return r >> 2, bool(r & 1), bool(r & 2)
+
+
+def low_word_zero(x):
+    return int(np.float64(x).view(np.uint64)) & 0xFFFFFFFF == 0
+
+
+def test_symbol_clock_threshold_of_the_header(model):
+    for sps, _ in PAIRS:
+        thr = sps / 2.0 - 0.5
+        assert np.float64(model.model_threshold(thr)).view(np.uint64) == np.float64(symbol_clock_threshold(thr)).view(np.uint64), sps
+    for thr in (math.inf, -math.inf, math.nan):
+        assert math.isnan(model.model_threshold(thr))
+
+
+@pytest.mark.parametrize("sps,lock", PAIRS)
+def test_step_form_of_every_preset(model, sps, lock):
+    # the event step exactly where its preconditions hold and a word has few enough symbols for it to pay, the hand-scheduled step
+    # elsewhere (fsk_9600 at 5 samples per symbol among them); LM0 / NS0 from the low words of lock_rate - 1 and sps
+    tp = symbol_clock_threshold(sps / 2.0 - 0.5)
+    want = EVENT if model.model_ok(sps, lock, tp, 0.0) and sps >= 16.0 else HAND
+    lm0, ns0 = low_word_zero(lock - 1.0), low_word_zero(sps)
+    assert choose(model, [(sps, lock, 0.0)]) == (want, lm0, ns0)
+    assert choose(model, [(sps, lock, 0.0)], event=False) == (HAND, lm0, ns0)
+    if sps == 5.0:
+        assert want == HAND
+
+
+def test_step_form_of_a_batch(model):
+    assert choose(model, [(40.0, 0.77, 0.0), (40.0, 0.75, -3.5)]) == (EVENT, False, True)
+    assert choose(model, [(40.0, 0.75, 0.0), (48000 / 1800, 0.75, 0.0)]) == (EVENT, True, False)
+    assert choose(model, [(40.0, 0.75, 0.0), (5.0, 0.88, 0.0)]) == (HAND, False, True)       # one job below 16 samples per symbol
+    assert choose(model, [(40.0, 0.75, 0.0), (40.0, 0.75, 3000.0)]) == (HAND, True, True)    # one clock beyond pm_event_ok's range
+    assert choose(model, [(40.0, 0.77, 0.0), (40.0, 0.45, 0.0)])[0] == COMPARE
+
+
+@pytest.mark.parametrize("sps,lock,clk0", [(40.0, 0.45, 0.0), (40.0, 0.3, 0.0), (5.0, 0.45, 0.0), (40.0, 0.77, math.nan),
+                                           (40.0, 0.77, math.inf), (math.inf, 0.77, 0.0), (math.nan, 0.77, 0.0)])
+def test_step_form_falls_back_to_the_compare(model, sps, lock, clk0):
+    # lock_rate - 1 not exact (the fma form needs it), a clock or samples per symbol that are not finite: the reference's compare
+    if lock in (0.45, 0.3):
+        assert (lock - 1.0) + 1.0 != lock
+    assert choose(model, [(sps, lock, clk0)]) == (COMPARE, False, False)
