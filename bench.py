@@ -8,11 +8,13 @@ By default successive steps are pipelined the way a service decoding one recordi
 (chain_execute.RecordingPipeline, --overlap 2): demod kernels, slicer streams and host stages of neighbouring steps overlap;
 all K steps complete inside the timed region.  --overlap 0 times them strictly one after the other.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--samples S] [--chains-per-gpu C] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--samples S] [--chains-per-gpu C] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Prints ONE JSON line on rank 0 with `roofline` (dominant GPU kernel, HIP-event time measured inside the timed region
-through pm_prof_*) and `cpu_baseline` (the oracle -- the CPU restatement of the reference -- on a bounded sample).
+through pm_prof_*).  A plain run does only what that line's headline needs: set-up, warm-up, the timed steps, --dump-outputs.
+--full adds everything else, each in runs of its own: `cpu_baseline` (the oracle -- the CPU restatement of the reference -- on a
+bounded sample), the exchange leg, the `also` workloads, the N > 1 legs, the kernels alone and the upload legs.
 """
 import argparse
 import json
@@ -137,7 +139,13 @@ def main():
     ap.add_argument("--samples", type=int, default=28_800_000, help="samples per recording (10 min @ 48 kHz)")
     ap.add_argument("--chains-per-gpu", type=int, default=0)
     ap.add_argument("--rate", type=int, default=48000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, everything else the line can carry, each in runs of its own: the CPU baseline, the exchange leg "
+                         "(--with-exchange), the `also` workloads (--also), an N > 1 line's `strong` and `also.qpsk_2400_64`, and after the timed "
+                         "steps the kernels alone (roofline.alone), the upload leg (value_with_h2d_overlapped) and the upload itself (h2d).  "
+                         "Without it a run sets up (with the communicator of --with-exchange), warms up, times the steps, writes --dump-outputs "
+                         "and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--overlap", type=int, default=2,
                     help="how successive steps (recordings) overlap, as in a service decoding one recording after another. "
                          "2: three-stage pipeline (chain_execute.RecordingPipeline): demod of step k+1 on the default stream, slicer of "
@@ -162,15 +170,16 @@ def main():
                          "give 16384 loops in flight (every lane of one stepping wave per CU), never more than --steps")
     ap.add_argument("--loop-chunk", type=int, default=0, help="carrier-loop workloads: final-filter outputs per time chunk (0: 65536 for runs of "
                     "more than 8192 loops, 131072 from 2048 recordings, else 262144 -- the work buffers are sized by it)")
-    ap.add_argument("--also", type=int, default=1, help="1 (default, one GPU only): after the headline workload also measure fsk_9600, "
+    ap.add_argument("--also", type=int, default=1, help="--full, 1 (default, one GPU only): after the headline workload also measure fsk_9600, "
                     "bpsk_300 and qpsk_2400 (BASELINE configs[2], [1], [4]) briefly and attach them under 'also'")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the headline workload's last step returned (its packet table) to DIR/*.npy "
                          "(see dump_outputs), for comparing the outputs of two builds")
     ap.add_argument("--with-exchange", type=int, default=1,
-                    help="1 (default): a one-GPU line also carries value_with_exchange -- the same timed steps with the packet exchange "
+                    help="1 (default): a one-GPU line is measured with a one-rank communicator up, made before the executor's streams as a "
+                         "rank of an N > 1 run has it, and with --full also carries value_with_exchange -- the same timed steps with the packet exchange "
                          "(one-rank RCCL gather + rank 0's de-dup over gathered rows) behind the executor, what every rank of an N > 1 run "
-                         "does -- so that the first step of a 1 -> N curve compares like with like; an N > 1 weak-scaling line also carries "
+                         "does -- so that the first step of a 1 -> N curve compares like with like; an N > 1 weak-scaling --full line also carries "
                          "`strong`: the config's own chains divided over the ranks (one chain per GPU at N = 8)")
     args = ap.parse_args()
 
@@ -190,9 +199,9 @@ def main():
         args.gpus = world                             # the launcher's word: one process per GPU
 
     # CPU baseline first: it forks one process per chain, which must happen before this process initialises the GPU.  Rank 0 of every
-    # run carries it (N > 1: the other ranks wait for rank 0 in the rendezvous meanwhile; a self-launched run has it from the parent).
+    # --full run carries it (N > 1: the other ranks wait for rank 0 in the rendezvous meanwhile; a self-launched run has it from the parent).
     cpu_line, cpu_also = None, {}
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         handed = os.environ.get("BENCH_CPU_BASELINE_FILE")
         if handed and os.path.exists(handed):
             cpu_line = json.load(open(handed))
@@ -237,18 +246,22 @@ def main():
                 dist.init_process_group("nccl", device_id=torch.device("cuda", dev_index), pg_options=opts)
         else:
             dist.init_process_group(args.backend)
-    exchange_leg = world == 1 and not use_dist and bool(args.with_exchange) and args.overlap == 2
+    one_rank_comm = world == 1 and not use_dist and bool(args.with_exchange) and args.overlap == 2
+    exchange_leg = args.full and one_rank_comm
     comm_up = False
-    if use_dist or (exchange_leg and os.environ.get("BENCH_EXCHANGE_COMM_FIRST", "1") != "0"):
-        # (the one-GPU line's exchange leg: its communicator comes up HERE, before the first stream of the executor exists, as in every
-        # rank of an N > 1 run -- made afterwards it leaves the exchange 30 % slower, profiles/r04_exchange_probe.txt; the headline steps
-        # below do not use it)
+    if use_dist or (one_rank_comm and os.environ.get("BENCH_EXCHANGE_COMM_FIRST", "1") != "0"):
+        # (the one-GPU line's communicator comes up HERE, before the first stream of the executor exists, as in every rank of an N > 1
+        # run, in a plain run too.  The headline steps below do not use it, but its streams share the GPU's hardware queues with the
+        # executor's: without it the same steps took 0.50-0.51 instead of 0.68 ms at 400 steps, 0.71-0.75 instead of 0.82-0.87 at 20, so
+        # it is part of what `value` measures.  --full's exchange leg runs over it: made afterwards it leaves the exchange 30 % slower,
+        # profiles/r04_exchange_probe.txt)
         try:
             init_dist()
             comm_up = True
-        except Exception:                                     # noqa: BLE001 -- the leg reports its own failure below
+        except Exception as e:                                # noqa: BLE001 -- --full: the exchange leg reports its own failure below
             if use_dist:
                 raise
+            print(f"bench.py: no one-rank communicator, the headline runs without one: {e!r}", file=sys.stderr)
     coll_device = f"cuda:{dev_index}" if (use_dist and args.backend == "nccl") else None
 
     env = {"rank": rank, "world": world, "dev_index": dev_index, "use_dist": use_dist, "coll_device": coll_device}
@@ -274,7 +287,7 @@ def main():
                                             "de-dup over them): the N = 1 point of a 1 -> N curve whose other points all exchange"}
         except Exception as e:                                # noqa: BLE001 -- never allowed to break the main line
             out["with_exchange"] = {"error": repr(e)[:300]}
-    if world > 1 and args.scaling == "weak" and args.with_exchange:
+    if args.full and world > 1 and args.scaling == "weak" and args.with_exchange:
         # north_star's own sharding -- the config's chains divided over the GPUs, one chain per GPU at N = 8 -- beside the weak-scaling
         # figure, same steps, same exchange (every rank runs it: the collectives inside must line up)
         a = copy.copy(args)
@@ -284,7 +297,7 @@ def main():
             out["strong"] = {"value": d3["value"], "unit": d3["unit"], "ms_per_step": d3["ms_per_step"], "steps": d3["steps"],
                              "chains_total": d3["config"]["chains_total"], "parallelism": d3["config"]["parallelism"],
                              "packets": d3.get("packets"), "scaling": "strong"}
-    if world > 1 and args.also:
+    if args.full and world > 1 and args.also:
         # BASELINE configs[4]'s own curve: the 64 chains of the qpsk_2400 sweep divided over the ranks (8 per GPU at N = 8, what
         # north_star names), every rank one engine run of as many recordings as give it 24 576 loops in flight, the packet exchange and
         # rank 0's de-dup over all 64 chains behind it.  Every rank runs it: the collectives inside must line up.  The N = 1 point of the
@@ -310,7 +323,7 @@ def main():
     if rank == 0:
         if cpu_line is not None:
             out["cpu_baseline"] = cpu_line
-        if world == 1 and args.also:
+        if args.full and world == 1 and args.also:
             out["also"] = also_workloads(args, env, cpu_also)
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(out) + "\n").encode())         # the ONE line of this run's stdout
@@ -375,7 +388,7 @@ def matrix_roofline(native, args, modems, my, prof):
 
 def self_launch(args):
     """`python bench.py --gpus N` (N > 1) with no launcher around it: this process -- which never touches the GPU -- runs the CPU
-    baseline, then starts `python -m torch.distributed.run --nnodes=1 --nproc-per-node N bench.py <the same arguments>` as a CHILD
+    baseline (--full), then starts `python -m torch.distributed.run --nnodes=1 --nproc-per-node N bench.py <the same arguments>` as a CHILD
     (never an exec: a process that holds the GPU must not be replaced, and this one may have forked already), relays rank 0's one
     JSON line and returns the child's exit code.  (pymodem.py:140-166: the reference's own one-process-per-chain launch.)"""
     import socket
@@ -384,7 +397,7 @@ def self_launch(args):
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     tmp = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         factory, default_cpg, _ = WORKLOADS[args.workload]
         cpu_line = cpu_baseline(args, [factory(c) for c in range(args.chains_per_gpu or default_cpg)])
         fd, tmp = tempfile.mkstemp(prefix="bench_cpu_", suffix=".json")
@@ -500,7 +513,8 @@ def dump_outputs(table, directory):
 
 
 def measure(args, env):
-    """One workload: build the chain group, W warm-up steps, K timed steps -> the dict of the JSON line (rank 0) or None."""
+    """One workload: build the chain group, W warm-up steps, K timed steps (--full: then the kernels alone and the upload legs) -> the
+    dict of the JSON line (rank 0) or None."""
     import torch
     rank, world, dev_index, use_dist, coll_device = env["rank"], env["world"], env["dev_index"], env["use_dist"], env["coll_device"]
     import pymodem_amd
@@ -1088,7 +1102,7 @@ def measure(args, env):
     # the same kernels with the GPU to themselves (one more step, strictly sequential, outside the timed region): in the pipelined
     # run two or more streams share the CUs, which stretches every kernel's duration
     alone = {}
-    if native_exec[0] and args.overlap >= 2 and not loop_wl and not exchanging and args.steps > 1:
+    if args.full and native_exec[0] and args.overlap >= 2 and not loop_wl and not exchanging and args.steps > 1:
         # The native executor's own kernels with the GPU to themselves: the same pipeline, ONE recording in flight -- submitted, and its
         # result taken (demod, slicers and host stage drained) before the next is submitted.  Its demod stage then runs on one stream with
         # nothing beside it: the matrix-pipe kernels the timed region ran (round 4 timed the Python-sequenced path's binary64 kernels here).
@@ -1111,7 +1125,7 @@ def measure(args, env):
                 a0 = alone.get(name, (0.0, 0))
                 alone[name] = (a0[0] + ms, a0[1] + cnt)
             c_.profile(False)
-    elif args.overlap and not loop_wl:
+    elif args.full and args.overlap and not loop_wl:
         saved, args.overlap = args.overlap, 0
         if args.steps > 1:                                    # (not for the one-step carrier-loop workloads: 5-8 s per step)
             run_steps(1)                                      # the sequential path's own buffers and first launches
@@ -1146,7 +1160,7 @@ def measure(args, env):
     # end to end including the recording's way into HBM, overlapped: K more steps with every recording uploaded one step ahead
     h2d_overlapped = None
     pinned_source = False
-    if args.overlap >= 2 and not loop_wl:
+    if args.full and args.overlap >= 2 and not loop_wl:
         import ctypes
         from pymodem_amd._native import lib as _lib
         pinned_source = os.environ.get("BENCH_PIN_SOURCE", "1") != "0" and \
@@ -1165,11 +1179,13 @@ def measure(args, env):
     if pinned_source:
         _lib().pm_host_unpin(audio.ctypes.data_as(ctypes.c_void_p))
     # the recording's way into HBM, outside the timed region (the boundary hands over a host buffer): pageable int16 -> device
-    t_up = time.perf_counter()
-    d_again = ctx.upload(audio)
-    ctx.sync()
-    h2d_ms = (time.perf_counter() - t_up) * 1e3
-    del d_again
+    h2d_ms = None
+    if args.full:
+        t_up = time.perf_counter()
+        d_again = ctx.upload(audio)
+        ctx.sync()
+        h2d_ms = (time.perf_counter() - t_up) * 1e3
+        del d_again
 
     dinfo = dist_info(use_dist)                   # (a collective: every rank)
     if rank == 0:
@@ -1288,7 +1304,8 @@ def measure(args, env):
                                       "frac_f64_sustained": round(work[k][1] / (prof[k][0] * 1e-3) / 1e12 / FP64_SUSTAINED_TFLOPS, 5)}
                                   for k in stage if prof[k][0] > 0 and work[k][0] > 0},
             "gpu_kernel_ms_per_step": {k: round(v[0] / args.steps, 4) for k, v in prof.items() if v[1]},
-            "h2d": {"ms": round(h2d_ms, 3), "bytes": int(audio.nbytes),
+            "h2d": None if h2d_ms is None else {
+                    "ms": round(h2d_ms, 3), "bytes": int(audio.nbytes),
                     "value_with_h2d": round(float(args.samples) * nchains / (elapsed / args.steps + h2d_ms * 1e-3) / 1e6, 3),
                     "value_with_h2d_overlapped": None if h2d_overlapped is None else round(float(args.samples) * nchains * args.steps / h2d_overlapped / 1e6, 3),
                     "overlapped_source_page_locked": bool(pinned_source),

@@ -233,15 +233,15 @@ def test_bench_launches_its_own_ranks_and_relays_their_exit_code():
 
 @pytest.mark.gpu
 def test_bench_two_ranks_by_itself():
-    """The scaling bench's command with N = 2 and nothing around it: two ranks share the one GPU of the test box
+    """The scaling bench's --full command with N = 2 and nothing around it: two ranks share the one GPU of the test machine
     over gloo, rank 0's ONE line comes back through the parent with n_gpus 2, the CPU baseline the parent measured before any rank
     existed, the strong-scaling figure beside the weak one -- and `also.qpsk_2400_64`, BASELINE configs[4]'s own curve point: the 64
     chains of the qpsk sweep divided over the ranks (32 each here), one engine run per rank, the exchange and rank 0's de-dup over
-    all 64 behind it (here at rehearsal size -- 12 recordings of 400 000 samples -- the driver's command runs it in full)."""
+    all 64 behind it (here at rehearsal size -- 12 recordings of 400 000 samples -- the driver's command with --full runs it in full)."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", BENCH_ALSO64_RECORDINGS="12", BENCH_ALSO64_SAMPLES="400000")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "4", "--warmup", "1",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--steps", "4", "--warmup", "1",
                         "--cpu-sample", "480000"], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]

@@ -528,4 +528,7 @@ def test_bench_line_contract_with_and_without_the_exchange(tmp_path):
         for key in ("bound", "achieved", "peak", "unit", "frac", "traffic"):
             assert key in d["roofline"], key
         assert d["roofline"]["bound"] in ("hbm", "mfma") and abs(d["roofline"]["frac"] - d["roofline"]["achieved"] / d["roofline"]["peak"]) < 1e-3
+        # without --full no leg runs beside the headline's steps
+        assert not {"cpu_baseline", "also", "with_exchange", "strong"} & set(d), sorted(d)
+        assert d["h2d"] is None and d["value_with_h2d_overlapped"] is None and d["roofline"]["alone"] is None
     assert lines["plain"]["packets"] == lines["gather"]["packets"] and lines["plain"]["packets"]["unique_good"] > 0

@@ -2,7 +2,7 @@
 """Does the kernel trace agree with the bench line's HIP events?  usage: timed_region_check.py <rocprof dir> <bench line json> <out json>
 rocprofv3 --kernel-trace of one bench.py run gives every launch of the dominant kernel with its start and end; the run's own line gives
 the kernel's average duration over the TIMED steps from HIP events on its stream (roofline.avg_kernel_ms).  The trace's launches in start
-order are warm-up, timed steps, then the line's other legs (exchange, upload, the kernel alone): the timed ones are launches
+order are warm-up, timed steps, then (--full) the line's other legs (exchange, upload, the kernel alone): the timed ones are launches
 warmup+1 .. warmup+steps.  The --stats average of the whole run mixes all of those legs and is NOT the figure to compare."""
 import csv
 import glob
@@ -27,7 +27,7 @@ out = {"command": "rocprofv3 --kernel-trace --stats -- python3 bench.py " + " ".
        "trace_first_start_to_last_end_ms_per_step": round(span / k, 5),
        "agreement": round(sum(dur) / len(dur) / line["roofline"]["avg_kernel_ms"], 4),
        "note": "same process, same launches: the kernel trace's start/end of the timed launches against the HIP events bench.py records around "
-               "them on the demod streams.  The --stats average over all launches of the run also counts the exchange leg, the upload leg and the "
+               "them on the demod streams.  The --stats average over all launches of a --full run also counts the exchange leg, the upload leg and the "
                "kernel-alone leg of the same line"}
 json.dump(out, open(out_path, "w"), indent=1)
 print(json.dumps(out))
