@@ -9,7 +9,11 @@
 // (coalesced), the owning lanes iterate over it, then all lanes stream the output tile back; for the
 // AGC the 64 lanes also do the per-sample division, which is not part of the recurrence.
 //
-// Built with -ffp-contract=off; no fma is used here because the reference has none.
+// Built with -ffp-contract=off; no fma is used here because the reference has none (one exception, exact: the table index of pd_lookup).
+//
+// Round 3 rewrote the quantising statements into forms that differ from the reference's text (nco_update, pi_update, pd_lookup, the
+// MPSK control); each carries its argument in a comment below, and each argument is exercised where it decides by
+// tests/test_gpu_loop_edges.py on the reference-made cases of tests/golden/loop_edges.npz (the case names are given in brackets).
 #include "pm_common.h"
 #include <algorithm>
 #include <cstdlib>
@@ -69,6 +73,10 @@ __device__ __forceinline__ double iir1(double b0, double b1, double a1, double &
 // there, Sterbenz, and below 2pi) and the second none.  Both candidates' indices are computed side by side and the compare only
 // selects (round 3): the chain no longer runs through compare -> select -> add -> compare -> select before the multiplication,
 // ~45 cycles of ~370.  Anything else (negative, a turn or more per sample, NaN) takes the statements as written.
+// [slow: 70-87 % of the samples off the fast path, up to tens of trips; idx256, carry_2pi, carry_2pi_even, step_lt_half_ulp: a phase of
+// exactly 2 pi, reached by `-tiny + 2 pi` on the SLOW path -- the only way index 256 reaches the table read in any case, through the
+// clamp -- wrapped to 0.0 on the fast one and carried from call to call; below_2pi, step_gt_half_ulp: the last doubles below 2 pi, the
+// largest phase the fast path keeps, whose index is 255]
 __device__ __forceinline__ void nco_update(LoopRegs &L, const double2v *tab2)
 {
     const double ph0 = L.phase + L.phase_scaling * (L.set_frequency + L.control);   // nco.py:35
@@ -76,7 +84,7 @@ __device__ __forceinline__ void nco_update(LoopRegs &L, const double2v *tab2)
     const bool wrap = ph0 >= kTwoPi;
     const int i0 = (int)(ph0 * L.index_scaling), i1 = (int)(down * L.index_scaling);  // nco.py:40, int() truncates
     double ph = wrap ? down : ph0;
-    int idx = wrap ? i1 : i0;                                               // 0..256 on this path: the table read needs no clamp
+    int idx = wrap ? i1 : i0;                                               // 0..256 on this path: the table read needs no clamp [seen: 0..255, below_2pi]
     int at = idx;
     if (__builtin_expect(!(ph0 >= 0.0 && ph0 < 2.0 * kTwoPi), 0)) {
         ph = ph0;
@@ -91,7 +99,7 @@ __device__ __forceinline__ void nco_update(LoopRegs &L, const double2v *tab2)
     L.phase = ph;
     double2v sc = tab2[at];
     asm volatile("" : "+v"(sc));                                            // one unconditional ds_read_b128, no branch around it
-    L.sine = idx < 256 ? sc.x : L.sine;                                     // nco.py:41-45: index 256 keeps the old value
+    L.sine = idx < 256 ? sc.x : L.sine;                                     // nco.py:41-45: index 256 keeps the old value [idx256: a preset sine survives]
     L.cosine = sc.y;                                                        // nco.py:46-51
 }
 
@@ -113,7 +121,8 @@ __device__ __forceinline__ double pi_update(LoopRegs &L, double sample)
     double in = L.integral + L.gain * (L.i_rate * sample);               // pi_control.py:27
     // pi_control.py:28-31: `if I > limit: I = limit` / `if I < -limit: I = -limit` are min and max for every value that is not a
     // NaN (the integral never is: it is a clamped sum of finite products) -- one instruction each instead of compare + two selects,
-    // and they sit on the loop-carried path
+    // and they sit on the loop-carried path [rails, slow: hundreds of samples on either rail; int_on_*, int_in_*: started on a rail
+    // and one ulp inside it]
     in = __builtin_fmin(in, L.i_limit);
     in = __builtin_fmax(in, -L.i_limit);
     L.integral = in;
@@ -128,6 +137,8 @@ __device__ __forceinline__ int pd_lookup(const int32_t *tbl, double re, double i
     //   x * 64 * 0.5 == x * 32 bit for bit (powers of two: both products are exact wherever the reference does not overflow);
     //   clip(int(f), -63, 63) == int(clip(f, -63.0, 63.0)) for the integer-valued f = floor(..);
     //   Q1 T[r][i] | Q4 T[-i][r] | Q2 T[i][-r] | Q3 T[-r][-i]: rows and columns swap where the signs differ (0 counts as positive).
+    // [test_detector_grid_every_pair_on_the_device: every pair of k/32 for |k| <= 66, +-0.0, +-5e-324, +-63/32, +-2, +-1e300, a lane and
+    // one sample each, the result read back from the loop filter's x0]
     double fr = floor(re * 32.0), fi = floor(im * 32.0);
     const bool swap = (fr >= 0) != (fi >= 0);
     fr = fmin(fmax(fr, -63.0), 63.0);               // >= 64 -> 63, <= -64 -> -63
@@ -177,7 +188,7 @@ __device__ __forceinline__ void loop_step(LoopRegs &L, const double2v *tab2, con
         const double im = (ar * si) + (sr * ai);          // complexmath.py:17
         const int e = pd_lookup(pdt, re, im);             // psk.py:739
         const double lp = iir_update(L, (double)e);
-        L.control = rint(pi_update(L, lp));               // psk.py:740, round() is half-to-even
+        L.control = rint(pi_update(L, lp));               // psk.py:740, round() is half-to-even [ties: 503 exact halves]
         o0 = re;
         o1 = im;
     }
