@@ -361,6 +361,44 @@ int pm_slice_batch(pm_ctx *ctx, pm_slice_job *h_jobs, int njobs);           /* n
 #define PM_COMPACT_HEAD 80
 int pm_slice_compact(pm_ctx *ctx, const pm_slice_job *h_jobs, int njobs, void *d_block, size_t block_bytes, int64_t *h_offsets,
                      size_t *h_used);
+/* The bitstream stage behind the slicers, on the device: what the host stage otherwise does byte by byte with every stream -- the LFSR
+ * (lfsr.py:22-52) and the search for the places where a decoder has something to do (ax25.py:36-50,69-89, il2p.py:367-376).  A job is
+ * the `n` data bytes a slicer job left on the device (pm_slice_job.d_data, 8-byte aligned), the chain's LFSR (any 64-bit polynomial,
+ * the register it starts from) and its codec kind (pm_codec_create; -1: descramble only) with the IL2P codec's sync_tol.  Runs on
+ * the ctx stream behind whatever produced the bytes; d_block (8-byte aligned) may be page-locked host memory that the device reaches.
+ * For job j, at d_block + h_offsets[j]:
+ *   the record, PM_SCAN_HEAD = 32 bytes:
+ *       uint64  the LFSR's register behind the stream
+ *       int64   bail_bit: the first reset (a flag, or the zero that ends a run of seven ones or more) that lies 8000 bits or more behind
+ *               the reset before it (or the stream's start), -1: none.  The list ends in front of it: from the last flag before it
+ *               the host decodes byte by byte.  AX.25 only (else -1).
+ *       int64   the first bit after the last flag in front of the stream's end (or of the bail bit), -1: no flag.  AX.25 only.
+ *       int32   events in the list (AX.25), int32 set bits in the bitmap (IL2P)
+ *   the list,
+ *       kind 0: n / 19 + 2 places of 8 bytes, the first `events` of them {uint32 P, uint32 F}, ascending: P = the bit (0 = the top bit
+ *               of byte 0) of a flag's closing zero, F = the first bit after the flag in front of it (0xFFFFFFFF: none).  Listed are the
+ *               stream's first flag and every later flag whose zero is counted bit T of the bits since the last reset, stuffed zeros
+ *               left out, with (T & 7) == 7 and T >= 8 * 18 + 7: the flags that close a frame of 18 bytes or more in a decoder that
+ *               starts from its just-created state.  Places past `events` are not written.
+ *       kind 1: (n + 63) / 64 words of 8 bytes, bit k & 63 of word k >> 6 set when descrambled bytes k - 4 .. k (k >= 4) hold, ending at
+ *               one of byte k's eight bits, 24 bits within sync_tol of 0xF15E48 or 32 bits within sync_tol of 0x5D57DF7F
+ *       kind -1: nothing
+ *   the n descrambled bytes, padded with zeros to a multiple of 8.
+ * *h_used = bytes the batch needs; PM_ERR_CAPACITY (with *h_used set) if block_bytes is less.  n <= 2^29, njobs <= 64.  Tiles of
+ * pm_ctx_tune(ctx, "bitscan_tile_words", 1 .. 256) 64-bit words (0: the default, 256); results do not depend on it. */
+#define PM_SCAN_HEAD 32
+#define PM_SCAN_LIST_BYTES(kind, n) ((kind) == 0 ? 8 * ((n) / 19 + 2) : (kind) == 1 ? 8 * (((n) + 63) / 64) : 0)     /* the list's bytes: the descrambled bytes lie behind it */
+typedef struct pm_scan_job {
+    const uint8_t *d_data;
+    int64_t n;
+    uint64_t lfsr_poly;
+    uint64_t lfsr_state;             /* the register in front of the stream (a stream scanned in pieces: the record's of the piece before) */
+    int32_t lfsr_invert;
+    int32_t codec_kind;              /* 0 AX.25, 1 IL2P, -1 none */
+    int32_t sync_tol;
+    int32_t reserved;
+} pm_scan_job;
+int pm_stream_scan(pm_ctx *ctx, const pm_scan_job *h_jobs, int njobs, void *d_block, size_t block_bytes, int64_t *h_offsets, size_t *h_used);
 /* How many chunks (= walkers) a batch is cut into on this ctx, within 1024..16384 samples per chunk; 0 restores the default 16384.
  * Lane-steps are N (1 + m/L) for merge length m (10-20 k samples) and chunk length L, the depth is (L + longest merge) x the
  * step time: long chunks are cheap, short ones are quick.  Results do not depend on it. */
@@ -517,6 +555,13 @@ int pm_codec_set_source(pm_codec *c, int32_t source_decoder);
  * cap of them out, oldest first, with CRC and header validity filled (packet_meta.py:197-208). */
 int pm_codec_decode(pm_codec *c, const uint8_t *h_data, const int64_t *h_addr, int64_t n, int64_t *h_pending);
 int pm_codec_fetch(pm_codec *c, pm_packet *h_out, int64_t cap, int64_t *h_count);
+/* pm_codec_decode for a codec in its just-created state (PM_ERR_ARG otherwise) with the stream's pm_stream_scan record and list at
+ * h_scan (kind as the codec's; h_plain: the n descrambled bytes, inside the block or a copy).  AX.25 takes the places to start decoding
+ * from the event list instead of searching for them, IL2P jumps from sync candidate to sync candidate of the bitmap instead of testing
+ * every byte; packets, *h_pending and the state the decoder is left in are pm_codec_decode's. */
+int pm_codec_decode_scanned(pm_codec *c, const uint8_t *h_plain, const int64_t *h_addr, int64_t n, const void *h_scan, int64_t *h_pending);
+/* Bytes this codec has taken through its byte-by-byte machine so far, and bytes it has passed over (either may be NULL). */
+int pm_codec_walked(pm_codec *c, int64_t *h_walked, int64_t *h_jumped);
 
 /* The host half of a whole chain group in two calls (chain_execute.py:20-26 for every chain of the group at once): per job
  * pm_lfsr_unscramble into a library-owned buffer, then pm_codec_decode; per codec pm_codec_fetch into consecutive row blocks
@@ -537,6 +582,9 @@ typedef struct pm_host_job {
     int64_t addr_first;           /* delta[0] + ... + delta[i] (delta[0] = 0)                                                   */
     uint8_t *h_plain;             /* NULL, or n bytes: the LFSR's output is written here (and decoded from here) instead of a    */
                                   /* library-owned buffer -- for callers that want to see what the codec saw                    */
+    const void *h_scan;           /* NULL, or the job's part of a pm_stream_scan block (record, list, bytes), made from the same */
+                                  /* h_data, LFSR and codec kind: the descrambled bytes and the register come from there and the */
+                                  /* codec goes through pm_codec_decode_scanned (h_plain, if given, receives a copy of the bytes) */
 } pm_host_job;
 int pm_host_decode_batch(pm_host_job *jobs, int njobs, int threads);
 int pm_codec_fetch_batch(pm_codec *const *codecs, const int64_t *counts, int n, pm_packet *h_out, int threads);
@@ -577,6 +625,8 @@ int64_t pm_correlate_strided(void *h_records, int64_t stride, const int64_t *h_c
  *                    as chain_builder.py makes them) and pm_correlate over the chains in config order
  *   pm_pipe_wait     the recording's packet rows, per-chain counts and the de-dup result, in the library's memory until
  *                    pm_pipe_release
+ * With the context's switch pipe_scan (pm_ctx_tune, PM_PIPE_SCAN; read by pm_pipe_create, default 0) the slicer threads run pm_stream_scan
+ * behind pm_slice_compact, into the same block, and the host threads decode from its lists (pm_host_job.h_scan); results are the same.
  * Results equal process_chain on every chain + PacketMetaArray.Correlate, recording by recording.  One submitting thread.  The
  * device pointers inside the descs (taps) must stay valid for the pipeline's life; host arrays are copied by pm_pipe_create. */
 typedef struct pm_pipe_fir {         /* a sign-FIR group: sign(FIR(int16 audio)) as one bitmap (pm_fir_signs_i16) -- FSKModem.demod, fsk.py:149-159 */

@@ -84,7 +84,28 @@ class HostJob(ctypes.Structure):
     _fields_ = [("codec", ctypes.c_void_p), ("h_data", ctypes.c_void_p), ("h_addr", ctypes.c_void_p), ("n", ctypes.c_int64),
                 ("lfsr_poly", ctypes.c_uint64), ("lfsr_state", ctypes.c_uint64), ("pending", ctypes.c_int64),
                 ("lfsr_invert", ctypes.c_int32), ("status", ctypes.c_int32),
-                ("h_addr_delta", ctypes.c_void_p), ("addr_first", ctypes.c_int64), ("h_plain", ctypes.c_void_p)]
+                ("h_addr_delta", ctypes.c_void_p), ("addr_first", ctypes.c_int64), ("h_plain", ctypes.c_void_p),
+                ("h_scan", ctypes.c_void_p)]
+
+
+class ScanJob(ctypes.Structure):
+    """pm_scan_job"""
+    _fields_ = [("d_data", ctypes.c_void_p), ("n", ctypes.c_int64), ("lfsr_poly", ctypes.c_uint64), ("lfsr_state", ctypes.c_uint64),
+                ("lfsr_invert", ctypes.c_int32), ("codec_kind", ctypes.c_int32), ("sync_tol", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+SCAN_HEAD = 32        # PM_SCAN_HEAD
+
+
+def scan_list_bytes(kind, n):
+    """PM_SCAN_LIST_BYTES: the bytes of a job's list inside a pm_stream_scan block (the descrambled bytes lie behind it)."""
+    return 8 * (n // 19 + 2) if kind == 0 else 8 * ((n + 63) // 64) if kind == 1 else 0
+
+
+def scan_record_dtype():
+    """NumPy view of the 32-byte record a pm_stream_scan job's part of the block begins with."""
+    import numpy as np
+    return np.dtype([("lfsr_state", "<u8"), ("bail_bit", "<i8"), ("last_flag", "<i8"), ("events", "<i4"), ("candidates", "<i4")])
 
 
 class ChainDesc(ctypes.Structure):
@@ -274,6 +295,7 @@ _SIGS = {
     "pm_slicer_tune": ([_vp, _i64], _int),
     "pm_slicer_limits": ([_vp, _i64], _int),
     "pm_slice_compact": ([_vp, _vp, _int, _vp, ctypes.c_size_t, ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_size_t)], _int),
+    "pm_stream_scan": ([_vp, ctypes.POINTER(ScanJob), _int, _vp, ctypes.c_size_t, ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_size_t)], _int),
     "pm_slicer_stats": ([_vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_i64)], _int),
     "pm_chain_create": ([_vp, ctypes.POINTER(ChainDesc), ctypes.POINTER(_vp)], _int),
     "pm_chain_run": ([_vp, _vp, _i64, _int, _vp, _vp, _i64, ctypes.POINTER(_i64)], _int),
@@ -285,6 +307,8 @@ _SIGS = {
     "pm_codec_destroy": ([_vp], _int),
     "pm_codec_set_source": ([_vp, ctypes.c_int32], _int),
     "pm_codec_decode": ([_vp, _vp, _vp, _i64, ctypes.POINTER(_i64)], _int),
+    "pm_codec_decode_scanned": ([_vp, _vp, _vp, _i64, _vp, ctypes.POINTER(_i64)], _int),
+    "pm_codec_walked": ([_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)], _int),
     "pm_codec_fetch": ([_vp, _vp, _i64, ctypes.POINTER(_i64)], _int),
     "pm_host_decode_batch": ([ctypes.POINTER(HostJob), _int, _int], _int),
     "pm_codec_fetch_batch": ([ctypes.POINTER(_vp), ctypes.POINTER(_i64), _int, _vp, _int], _int),

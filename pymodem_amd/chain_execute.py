@@ -846,7 +846,7 @@ class NativePipeline:
     raises ValueError for anything else (use RecordingPipeline there)."""
 
     def __init__(self, chains, max_samples, address_distance, ctx=None, names=None, chain_ids=None, slots=0, slice_workers=0, slice_group=0,
-                 host_threads=0, decode_threads=0, slice_min_group=0, demod_streams=0, keep_slices=False):
+                 host_threads=0, decode_threads=0, slice_min_group=0, demod_streams=0, keep_slices=False, scan=False):
         import os
         demod_streams = demod_streams or int(os.environ.get("PYMODEM_AMD_PIPE_DEMOD_STREAMS", 0))
         slots = slots or int(os.environ.get("PYMODEM_AMD_PIPE_SLOTS", 0))              # tuning knobs (DESIGN.md 4.4b)
@@ -923,7 +923,16 @@ class NativePipeline:
         desc.address_distance, desc.max_samples = float(address_distance), int(max_samples)
         desc.keep_slices = int(bool(keep_slices))
         h = ctypes.c_void_p()
-        check(lib().pm_pipe_create(ctx.handle, ctypes.byref(desc), ctypes.byref(h)))
+        # scan: the bitstream stage on the device (pm_stream_scan behind the slicers, the codecs decode from its lists).  pm_pipe_create
+        # reads the switch from its context
+        if scan:
+            ctx.tune(pipe_scan=1)
+        try:
+            check(lib().pm_pipe_create(ctx.handle, ctypes.byref(desc), ctypes.byref(h)))
+        finally:
+            if scan:                                        # back to what the context read when it was made
+                e = os.environ.get("PM_PIPE_SCAN")
+                ctx.tune(pipe_scan=0 if e is None else int(e) if e.lstrip("-").isdigit() else 1)
         self._h = h
         self.nchains = n
         self.done_at_ms = {}                                # ticket -> when it left the last stage (host clock since the pipeline was made)

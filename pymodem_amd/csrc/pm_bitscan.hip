@@ -1,0 +1,437 @@
+// The bitstream stage behind the slicers, on the device (pm_stream_scan): per stream of slicer bytes
+//   - the LFSR's output (lfsr.py:22-52): output bit t = XOR over the set bits k of poly of input bit t - k, one lane per 64-bit word,
+//   - AX.25 streams: the flags at which Ax25::feed_many (pm_codec.cpp) calls take_from_last_flag -- the first flag and every flag that
+//     closes a frame of at least 18 bytes (ax25.py:36-50,69-89) -- as a list, in stream order,
+//   - IL2P streams: one bit per byte, set where the sync test of il2p.py:367-376 hits at one of the byte's eight bit offsets.
+// A stream is cut into tiles of at most 256 words, a workgroup a tile, a lane a word.  What a flag closes depends on the last RESET in
+// front of it (a flag, or the zero that ends a run of seven ones or more) and on the stuffed zeros dropped since: the tile launch leaves a
+// summary per tile, one wave per stream combines the summaries in order (what every tile starts from, the stream's record), the emit
+// launch writes the list.  No workgroup waits for another inside a launch; every write is a plain store at a place that follows from
+// prefix counts, so the lists come out sorted and nothing has to be cleared beforehand.
+// Bits are handled in STREAM order: bit i of a word is stream bit 64 w + i (the bytes' bits from the top, as the slicer packs them).
+#include "pm_common.h"
+#include <algorithm>
+#include <cstring>
+
+namespace {
+
+constexpr int kScanJobs = 64;
+constexpr int kLanes = 256;                 // lanes of a workgroup = most words of a tile
+constexpr int kBailSpan = 8000;             // bits without a reset after which the host's skim gives up (pm_codec.cpp: feed_many)
+constexpr int kCloseBits = 8 * 18 + 7;      // a closing flag's zero is counted bit 8 k + 7, k >= 18 (ax25.py:74-81)
+
+struct ScanJobs {
+    const uint8_t *data[kScanJobs];
+    uint64_t poly[kScanJobs], reg0[kScanJobs];
+    int64_t off[kScanJobs];                 // the job's record in the block
+    int32_t n[kScanJobs];                   // bytes (<= 2^29)
+    int32_t tile0[kScanJobs + 1];           // first tile of the job among the batch's
+    int8_t kind[kScanJobs], invert[kScanJobs], tol[kScanJobs];
+    int32_t njobs, tile_words;
+};
+
+// One tile as the tiles in front of it see it.  Positions are bits from the tile's start, -1: none.  Events at or behind `bail` (the
+// first event of the tile whose span since a reset INSIDE the tile reaches kBailSpan) are left out of last_flag, first_flag and closing.
+struct TileSum {
+    int32_t dropped;                        // stuffed zeros in the tile
+    int32_t first_reset, dropped_to_first;  // the first reset and the stuffed zeros in front of it
+    int32_t last_reset, dropped_after_last;
+    int32_t first_flag, last_flag;
+    int32_t closing;                        // AX.25: closing flags whose reset lies inside the tile; IL2P: candidates
+    int32_t bail;
+    int32_t bits;                           // 1: the first reset is a flag, 2: the first flag is counted in `closing`
+    int32_t pad[2];
+};
+
+// What a tile starts from, left by the combine launch for the emit launch.
+struct TileCarry {
+    int64_t after_reset;                    // first bit after the last reset in front of the tile (0: none yet)
+    int64_t after_flag;                     // first bit after the last flag in front of it, -1: none
+    int64_t bail;                           // the stream's bail bit if it lies in this tile, -1 otherwise
+    int32_t dropped;                        // stuffed zeros between after_reset and the tile
+    int32_t events;                         // events of the tiles in front; -1: the stream has bailed before this tile
+};
+
+__device__ inline uint64_t load_word(const uint8_t *d, int64_t n, int64_t w)
+{
+    // input word w in stream order; bytes past the stream's end read as zero
+    if (w < 0 || 8 * w >= n) return 0;
+    uint64_t v = 0;
+    if (8 * w + 8 <= n) {
+        v = *reinterpret_cast<const uint64_t *>(d + 8 * w);
+    } else {
+        for (int i = 0; i < (int)(n - 8 * w); ++i) v |= (uint64_t)d[8 * w + i] << (8 * i);
+    }
+    return __brevll(__builtin_bswap64(v));
+}
+
+__device__ inline uint64_t plain_word(const ScanJobs &J, int j, int64_t w, uint64_t cur, uint64_t prev)
+{
+    // the LFSR's output word from input word w and the one before it
+    uint64_t o = 0;
+    for (uint64_t p = J.poly[j]; p; p &= p - 1) {
+        const int k = __builtin_ctzll(p);
+        o ^= k ? (cur << k) | (prev >> (64 - k)) : cur;
+    }
+    if (w == 0) o ^= J.reg0[j];             // bit t of the incoming register meets stream bit t
+    return J.invert[j] ? ~o : o;
+}
+
+// segment of consecutive words for the tile's one scan: stuffed zeros, the last reset with the zeros up to it, the last flag
+struct Seg {
+    int32_t s, ev, cs, fl;
+};
+__device__ inline Seg seg_join(const Seg &a, const Seg &b)
+{
+    Seg r;
+    r.s = a.s + b.s;
+    r.ev = b.ev >= 0 ? b.ev : a.ev;
+    r.cs = b.ev >= 0 ? a.s + b.cs : a.cs;
+    r.fl = b.fl >= 0 ? b.fl : a.fl;
+    return r;
+}
+
+template <class T, class Op>
+__device__ inline T block_scan(T v, T *lds, Op op)      // inclusive over the workgroup's lanes; lds[t] holds lane t's result afterwards
+{
+    const int t = threadIdx.x;
+    lds[t] = v;
+    __syncthreads();
+    for (int d = 1; d < kLanes; d <<= 1) {
+        const bool has = t >= d;
+        T o = v;
+        if (has) o = lds[t - d];
+        __syncthreads();
+        if (has) {
+            v = op(o, v);
+            lds[t] = v;
+        }
+        __syncthreads();
+    }
+    return v;
+}
+
+// the AX.25 patterns of one word (pm_codec.cpp: feed_many): stuffed zeros, resets, flags
+struct Marks {
+    uint64_t S, ev, flag;
+};
+__device__ inline Marks ax25_marks(uint64_t w, uint64_t prev, uint64_t valid)
+{
+    const uint64_t e1 = (w << 1) | (prev >> 63), e2 = (w << 2) | (prev >> 62), e3 = (w << 3) | (prev >> 61), e4 = (w << 4) | (prev >> 60),
+                   e5 = (w << 5) | (prev >> 59), e6 = (w << 6) | (prev >> 58), e7 = (w << 7) | (prev >> 57);
+    const uint64_t o5 = e1 & e2 & e3 & e4 & e5;
+    Marks m;
+    m.S = ~w & o5 & ~e6 & valid;
+    m.ev = ~w & o5 & e6 & valid;
+    m.flag = m.ev & ~e7;
+    return m;
+}
+
+// Lane state for its word's events: where the tile's last reset / flag in front of the word lie (bits from the tile's start; -1: none
+// inside the tile) and the stuffed zeros up to there and up to the word.  fn(P, is_flag, R, dropped, F): the event at bit P; R: first
+// bit after the reset in front of it inside the tile (-1: none, `dropped` then counts from the tile's start); F likewise for flags.
+struct LaneIn {
+    Marks m;
+    int32_t base, R, sR, exS, F;
+};
+template <class Fn>
+__device__ inline void walk_events(const LaneIn &in, Fn fn)
+{
+    int32_t R = in.R, sR = in.sR, F = in.F;
+    for (uint64_t e = in.m.ev; e; e &= e - 1) {
+        const int i = __builtin_ctzll(e);
+        const int32_t P = in.base + i, here = in.exS + __popcll(in.m.S & ((1ull << i) - 1));
+        const bool is_flag = (in.m.flag >> i) & 1;
+        if (!fn(P, is_flag, R, here - sR, F)) return;
+        R = P + 1;
+        sR = here;
+        if (is_flag) F = P + 1;
+    }
+}
+
+__device__ inline LaneIn lane_prepare(const Marks &m, bool active, Seg *lds, Seg *total)
+{
+    Seg mine{0, -1, 0, -1};
+    if (active) {
+        mine.s = __popcll(m.S);
+        if (m.ev) {
+            const int hi = 63 - __builtin_clzll(m.ev);
+            mine.ev = (int)threadIdx.x * 64 + hi;
+            mine.cs = __popcll(m.S & ((2ull << hi) - 1));
+        }
+        if (m.flag) mine.fl = (int)threadIdx.x * 64 + 63 - __builtin_clzll(m.flag);
+    }
+    block_scan(mine, lds, [](const Seg &a, const Seg &b) { return seg_join(a, b); });
+    const Seg before = threadIdx.x ? lds[threadIdx.x - 1] : Seg{0, -1, 0, -1};
+    *total = lds[kLanes - 1];
+    __syncthreads();
+    LaneIn in;
+    in.m = m;
+    if (!active) in.m.ev = 0;
+    in.base = (int)threadIdx.x * 64;
+    in.R = before.ev >= 0 ? before.ev + 1 : -1;
+    in.sR = before.ev >= 0 ? before.cs : 0;
+    in.exS = before.s;
+    in.F = before.fl >= 0 ? before.fl + 1 : -1;
+    return in;
+}
+
+__device__ inline bool closes(int64_t T) { return (T & 7) == 7 && T >= kCloseBits; }
+
+__device__ inline int job_of_tile(const ScanJobs &J, int tile)
+{
+    int j = 0;
+    while (j + 1 < J.njobs && J.tile0[j + 1] <= tile) ++j;
+    return j;
+}
+
+__host__ __device__ inline int64_t list_bytes(int kind, int64_t n) { return PM_SCAN_LIST_BYTES(kind, n); }
+
+// Launch 1: per tile the descrambled bytes, the IL2P bitmap, the tile's summary.
+__global__ __launch_bounds__(kLanes) void bitscan_tile_kernel(ScanJobs J, uint8_t *block, TileSum *sums)
+{
+    __shared__ Seg lds[kLanes];
+    __shared__ TileSum ts;
+    const int tile = blockIdx.x, j = job_of_tile(J, tile), tw = J.tile_words;
+    const int64_t n = J.n[j], nw = (n + 7) / 8;
+    const int64_t w = (int64_t)(tile - J.tile0[j]) * tw + threadIdx.x;
+    const bool active = (int)threadIdx.x < tw && w < nw;
+    const int kind = J.kind[j];
+    const uint8_t *d = J.data[j];
+    uint8_t *base = block + J.off[j], *list = base + PM_SCAN_HEAD, *plain = list + list_bytes(kind, n);
+    uint64_t x = 0, xp = 0, valid = 0;
+    if (active) {
+        const uint64_t i0 = load_word(d, n, w), i1 = load_word(d, n, w - 1), i2 = load_word(d, n, w - 2);
+        const int64_t have = n - 8 * w;
+        valid = have >= 8 ? ~0ull : (1ull << (8 * have)) - 1;
+        x = plain_word(J, j, w, i0, i1) & valid;
+        xp = w ? plain_word(J, j, w - 1, i1, i2) : 0;           // (a fresh decoder: zeros in front of the stream)
+        *reinterpret_cast<uint64_t *>(plain + 8 * w) = __builtin_bswap64(__brevll(x));       // the bytes are padded to 8: the last store is whole
+    }
+    if (threadIdx.x == 0) {
+        ts = TileSum{0, -1, 0, -1, 0, -1, -1, 0, -1, 0, {0, 0}};
+        ts.bail = 0x7FFFFFFF;
+    }
+    __syncthreads();
+    if (kind == 1) {
+        // il2p.py:367-376 at the eight bit offsets of every byte k >= 4: the 32 bits in front of each against both patterns
+        if (active) {
+            const uint64_t C = __brevll(x), P = __brevll(xp);   // most significant bit first: byte 0 on top
+            const int tol = J.tol[j];
+            unsigned bits = 0;
+            for (int b = 0; b < 8; ++b) {
+                const int64_t k = 8 * w + b;
+                if (k < 4 || k >= n) continue;
+                const int sh = 8 * (7 - b);
+                const uint64_t win = (sh ? (C >> sh) | (P << (64 - sh)) : C) & 0xFFFFFFFFFFull;
+                bool hit = false;
+                for (int s = 0; s < 8; ++s) {
+                    const uint32_t v = (uint32_t)(win >> (7 - s));
+                    hit = hit || __popc((v & 0xFFFFFFu) ^ 0xF15E48u) <= tol || __popc(v ^ 0x5D57DF7Fu) <= tol;
+                }
+                bits |= (unsigned)hit << b;
+            }
+            list[w] = (uint8_t)bits;
+            if (w == nw - 1)
+                for (int64_t q = nw; q < ((nw + 7) & ~int64_t(7)); ++q) list[q] = 0;
+            if (bits) atomicAdd(&ts.closing, __popc(bits));
+        }
+    } else if (kind == 0) {
+        Seg total;
+        const LaneIn in = lane_prepare(ax25_marks(x, xp, valid), active, lds, &total);
+        int cand = 0x7FFFFFFF;
+        walk_events(in, [&](int32_t P, bool, int32_t R, int32_t, int32_t) {
+            if (R >= 0 && P - R >= kBailSpan) {
+                cand = P;
+                return false;
+            }
+            return true;
+        });
+        if (cand != 0x7FFFFFFF) atomicMin(&ts.bail, cand);
+        __syncthreads();
+        const int limit = ts.bail;
+        int closing = 0, last_flag = -1;
+        walk_events(in, [&](int32_t P, bool is_flag, int32_t R, int32_t dropped, int32_t F) {
+            if (P >= limit) return false;
+            if (R < 0) {                                        // the tile's first reset: one lane meets it
+                ts.first_reset = P;
+                ts.dropped_to_first = dropped;
+                if (is_flag) atomicOr(&ts.bits, 1);
+            }
+            if (is_flag) {
+                const bool c = R >= 0 && closes((int64_t)(P - R) - dropped);
+                if (F < 0) {                                    // the tile's first flag
+                    ts.first_flag = P;
+                    if (c) atomicOr(&ts.bits, 2);
+                }
+                closing += c;
+                last_flag = P;
+            }
+            return true;
+        });
+        if (closing) atomicAdd(&ts.closing, closing);
+        if (last_flag >= 0) atomicMax(&ts.last_flag, last_flag);
+        if (threadIdx.x == 0) {
+            ts.dropped = total.s;
+            ts.last_reset = total.ev;
+            ts.dropped_after_last = total.ev >= 0 ? total.s - total.cs : total.s;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (ts.bail == 0x7FFFFFFF) ts.bail = -1;
+        sums[tile] = ts;
+    }
+}
+
+// Launch 2: a wave per stream takes the summaries in order, 64 at a time (a lane loads one, all lanes step through them together).
+__global__ __launch_bounds__(64) void bitscan_combine_kernel(ScanJobs J, uint8_t *block, const TileSum *sums, TileCarry *carries)
+{
+    const int j = blockIdx.x, lane = threadIdx.x, tw = J.tile_words;
+    const int t0 = J.tile0[j], nt = J.tile0[j + 1] - t0;
+    const int kind = J.kind[j];
+    int64_t R = 0, LF = -1, bail = -1;
+    int32_t since = 0, events = 0, cands = 0;
+    for (int r0 = 0; r0 < nt; r0 += 64) {
+        TileSum s = TileSum{0, -1, 0, -1, 0, -1, -1, 0, -1, 0, {0, 0}};
+        if (r0 + lane < nt) s = sums[t0 + r0 + lane];
+        TileCarry mine{0, -1, -1, 0, -1};
+        for (int l = 0; l < 64 && r0 + l < nt; ++l) {
+            const int32_t dropped = __shfl(s.dropped, l), first_reset = __shfl(s.first_reset, l), dropped_to_first = __shfl(s.dropped_to_first, l),
+                          last_reset = __shfl(s.last_reset, l), dropped_after_last = __shfl(s.dropped_after_last, l), first_flag = __shfl(s.first_flag, l),
+                          last_flag = __shfl(s.last_flag, l), closing = __shfl(s.closing, l), tbail = __shfl(s.bail, l), bits = __shfl(s.bits, l);
+            const int64_t B = (int64_t)(r0 + l) * tw * 64;
+            TileCarry c{R, LF, -1, since, bail >= 0 ? -1 : events};
+            cands += closing;
+            if (kind == 0 && bail < 0) {
+                if (first_reset >= 0) {
+                    const int64_t P0 = B + first_reset, span = P0 - R;
+                    if (span >= kBailSpan) {
+                        bail = c.bail = P0;
+                    } else {
+                        if (bits & 1) {
+                            if (LF < 0 || closes(span - (since + dropped_to_first))) ++events;
+                        } else if (LF < 0 && first_flag >= 0 && !(bits & 2)) {
+                            ++events;                           // the stream's first flag, whatever it closes
+                        }
+                        events += closing;
+                        if (last_flag >= 0) LF = B + last_flag + 1;
+                        if (tbail >= 0) {
+                            bail = c.bail = B + tbail;
+                        } else {
+                            R = B + last_reset + 1;
+                            since = dropped_after_last;
+                        }
+                    }
+                } else {
+                    since += dropped;
+                }
+            }
+            if (l == lane) mine = c;
+        }
+        if (r0 + lane < nt) carries[t0 + r0 + lane] = mine;
+    }
+    if (lane == 0) {
+        // the register as the stream leaves it (lfsr.py:30-51): what is left of the incoming one, and the taps of the last 63 input bits
+        const int64_t n = J.n[j], T = 8 * n;
+        uint64_t reg = T < 64 ? J.reg0[j] >> T : 0;
+        for (int64_t t = T > 63 ? T - 63 : 0; t < T; ++t)
+            if ((J.data[j][t >> 3] >> (7 - (t & 7))) & 1) reg ^= J.poly[j] >> (T - t);
+        uint8_t *rec = block + J.off[j];
+        *reinterpret_cast<uint64_t *>(rec) = reg;
+        *reinterpret_cast<int64_t *>(rec + 8) = bail;
+        *reinterpret_cast<int64_t *>(rec + 16) = kind == 0 ? LF : -1;
+        *reinterpret_cast<int32_t *>(rec + 24) = kind == 0 ? events : 0;
+        *reinterpret_cast<int32_t *>(rec + 28) = kind == 1 ? cands : 0;
+    }
+}
+
+// Launch 3: the events of every AX.25 tile, at the places the combine counted out.
+__global__ __launch_bounds__(kLanes) void bitscan_emit_kernel(ScanJobs J, uint8_t *block, const TileCarry *carries)
+{
+    __shared__ Seg lds[kLanes];
+    __shared__ int32_t cnt[kLanes];
+    const int tile = blockIdx.x, j = job_of_tile(J, tile), tw = J.tile_words;
+    if (J.kind[j] != 0) return;
+    const TileCarry c = carries[tile];
+    if (c.events < 0) return;
+    const int64_t n = J.n[j], nw = (n + 7) / 8;
+    const int64_t tbase = (int64_t)(tile - J.tile0[j]) * tw, w = tbase + threadIdx.x, B = tbase * 64;
+    const bool active = (int)threadIdx.x < tw && w < nw;
+    uint64_t x = 0, xp = 0, valid = 0;
+    if (active) {
+        const uint8_t *d = J.data[j];
+        const uint64_t i0 = load_word(d, n, w), i1 = load_word(d, n, w - 1), i2 = load_word(d, n, w - 2);
+        const int64_t have = n - 8 * w;
+        valid = have >= 8 ? ~0ull : (1ull << (8 * have)) - 1;
+        x = plain_word(J, j, w, i0, i1) & valid;
+        xp = w ? plain_word(J, j, w - 1, i1, i2) : 0;
+    }
+    Seg total;
+    const LaneIn in = lane_prepare(ax25_marks(x, xp, valid), active, lds, &total);
+    const int64_t limit = c.bail >= 0 ? c.bail : INT64_MAX;
+    // a closing flag has 151 counted bits behind it: a word holds one at most, and the stream's first flag beside it
+    uint2 found[2];
+    int nfound = 0;
+    walk_events(in, [&](int32_t P, bool is_flag, int32_t R, int32_t dropped, int32_t F) {
+        const int64_t Pa = B + P;
+        if (Pa >= limit) return false;
+        if (!is_flag) return true;
+        const int64_t T = R >= 0 ? (int64_t)(P - R) - dropped : (Pa - c.after_reset) - ((int64_t)c.dropped + dropped);
+        const int64_t Fa = F >= 0 ? B + F : c.after_flag;
+        if ((Fa < 0 || closes(T)) && nfound < 2) found[nfound++] = make_uint2((uint32_t)Pa, (uint32_t)Fa);
+        return true;
+    });
+    block_scan((int32_t)nfound, cnt, [](int32_t a, int32_t b) { return a + b; });
+    const int64_t at = (int64_t)c.events + (threadIdx.x ? cnt[threadIdx.x - 1] : 0), cap = n / 19 + 2;
+    uint2 *events = reinterpret_cast<uint2 *>(block + J.off[j] + PM_SCAN_HEAD);
+    for (int k = 0; k < nfound; ++k)
+        if (at + k < cap) events[at + k] = found[k];
+}
+
+}  // namespace
+
+extern "C" int pm_stream_scan(pm_ctx *ctx, const pm_scan_job *h_jobs, int njobs, void *d_block, size_t block_bytes, int64_t *h_offsets, size_t *h_used)
+{
+    PM_CTX(ctx);
+    PM_ARG(h_jobs && njobs >= 1 && njobs <= kScanJobs && d_block && ((uintptr_t)d_block & 7) == 0 && h_offsets && h_used);
+    ScanJobs J;
+    memset(&J, 0, sizeof(J));
+    J.njobs = njobs;
+    const int tune = ctx->tune.bitscan_tile_words;
+    J.tile_words = tune > 0 ? std::min(tune, kLanes) : kLanes;
+    size_t at = 0;
+    int64_t tiles = 0;
+    for (int j = 0; j < njobs; ++j) {
+        const pm_scan_job &q = h_jobs[j];
+        PM_ARG(q.n >= 0 && q.n <= (int64_t)1 << 29 && (q.n == 0 || (q.d_data && ((uintptr_t)q.d_data & 7) == 0)));
+        PM_ARG(q.codec_kind >= -1 && q.codec_kind <= 1);
+        J.data[j] = q.d_data;
+        J.poly[j] = q.lfsr_poly;
+        J.reg0[j] = q.lfsr_state;
+        J.n[j] = (int32_t)q.n;
+        J.kind[j] = (int8_t)q.codec_kind;
+        J.invert[j] = q.lfsr_invert != 0;
+        J.tol[j] = (int8_t)std::max(-1, std::min(33, q.sync_tol));
+        J.off[j] = h_offsets[j] = (int64_t)at;
+        J.tile0[j] = (int32_t)tiles;
+        at += PM_SCAN_HEAD + (size_t)list_bytes(q.codec_kind, q.n) + (size_t)((q.n + 7) & ~int64_t(7));
+        tiles += pm_cdiv(pm_cdiv(q.n, 8), J.tile_words);
+        PM_ARG(tiles < (int64_t)1 << 30);
+    }
+    J.tile0[njobs] = (int32_t)tiles;
+    *h_used = at;
+    if (at > block_bytes) return pm_set_error(PM_ERR_CAPACITY, "pm_stream_scan: the block holds %zu bytes, the batch needs %zu", block_bytes, at);
+    const size_t sums_bytes = ((size_t)tiles * sizeof(TileSum) + 63) & ~(size_t)63;
+    if (int rc = pm_scratch_reserve(ctx, sums_bytes + (size_t)tiles * sizeof(TileCarry) + 64)) return rc;
+    TileSum *sums = static_cast<TileSum *>(ctx->d_scratch);
+    TileCarry *carries = reinterpret_cast<TileCarry *>(static_cast<uint8_t *>(ctx->d_scratch) + sums_bytes);
+    uint8_t *block = static_cast<uint8_t *>(d_block);
+    if (tiles) hipLaunchKernelGGL(bitscan_tile_kernel, dim3((unsigned)tiles), dim3(kLanes), 0, ctx->stream, J, block, sums);
+    hipLaunchKernelGGL(bitscan_combine_kernel, dim3(njobs), dim3(64), 0, ctx->stream, J, block, sums, carries);
+    bool any = false;
+    for (int j = 0; j < njobs; ++j) any = any || (h_jobs[j].codec_kind == 0 && h_jobs[j].n > 0);
+    if (any) hipLaunchKernelGGL(bitscan_emit_kernel, dim3((unsigned)tiles), dim3(kLanes), 0, ctx->stream, J, block, carries);
+    PM_HIP(hipGetLastError());
+    return PM_OK;
+}

@@ -254,7 +254,13 @@ int rs_decode(int num_roots, uint8_t *buf, int n, int min_distance)
 struct pm_codec {
     Sink sink;
     int source = 0;
+    int kind = 0;
+    bool fresh = true;                                   // nothing fed yet: the state pm_stream_scan's lists are made for
+    int64_t walked = 0;                                  // bytes taken through the byte-by-byte machine (pm_codec_walked)
+    int64_t fed = 0;
     virtual ~pm_codec() {}
+    // feed_many for a fresh decoder with the stream's pm_stream_scan record and list; false: the list does not fit the stream
+    virtual bool feed_scanned(const uint8_t *d, const int64_t *a, int64_t n, const uint8_t *scan) = 0;
     virtual void feed(uint8_t byte, int64_t addr, Sink &sink) = 0;
     virtual void feed_many(const uint8_t *d, const int64_t *a, int64_t n)
     {
@@ -337,6 +343,7 @@ struct Ax25 : pm_codec {
     explicit Ax25(int src)
     {
         source = src;
+        kind = 0;
         static const bool on = [] {
             const char *e = getenv("PM_AX25_SKIM");         // =0: every byte through the table-driven decoder (rounds 2-4), for A/B runs and the tests
             return !(e && e[0] == '0');
@@ -455,9 +462,46 @@ struct Ax25 : pm_codec {
         take_from_last_flag(n);
     }
 
+    // feed_many with the events found on the device (pm_bitscan.hip): the same reposition / run calls in the same order, the flags that
+    // close something read from the list instead of searched for
+    bool feed_scanned(const uint8_t *d, const int64_t *a, int64_t n, const uint8_t *scan) override
+    {
+        if (!skim_on || n < 24) {
+            run(d, a, 0, n);
+            return true;
+        }
+        int64_t last_flag;
+        int32_t events;
+        memcpy(&last_flag, scan + 16, 8);
+        memcpy(&events, scan + 24, 4);
+        if (events < 0 || events > n / 19 + 2 || last_flag < -1 || last_flag > 8 * n) return false;
+        int64_t cursor = 0;
+        auto take_from = [&](int64_t LF, int64_t upto) {      // feed_many's take_from_last_flag
+            if (LF >= 0) {
+                const int64_t sb = (LF - 1) >> 3;
+                if (sb >= cursor && sb > 0) {
+                    reposition(d, sb);
+                    cursor = sb;
+                }
+            }
+            run(d, a, cursor, upto);
+            cursor = upto;
+        };
+        for (int32_t e = 0; e < events; ++e) {
+            uint32_t pf[2];
+            memcpy(pf, scan + PM_SCAN_HEAD + 8 * (size_t)e, 8);
+            const int64_t P = pf[0], F = pf[1] == 0xFFFFFFFFu ? -1 : (int64_t)pf[1];
+            if ((P >> 3) >= n || F > P || (P >> 3) + 1 < cursor) return false;
+            take_from(F, (P >> 3) + 1);
+        }
+        take_from(last_flag, n);                             // the registers as the call leaves them (after a bail: the rest through the table)
+        return true;
+    }
+
     // bytes [k0, k1) through the registers, eight bits at a time (round 2)
     void run(const uint8_t *d, const int64_t *a, int64_t k0, int64_t k1)
     {
+        walked += k1 - k0;
         // the collected bytes as a raw buffer while this call runs (one slot of slack: a byte is stored whether or not it is
         // complete and the length moves on only if it is -- no branch on the data)
         size_t len = data.size();
@@ -604,11 +648,35 @@ struct Il2p : pm_codec {
     {
         feasible = sync_feasible(tol);
         source = src;
+        kind = 1;
         memset(buf, 0, sizeof(buf));
     }
 
-    void feed_many(const uint8_t *d, const int64_t *a, int64_t n) override
+    void feed_many(const uint8_t *d, const int64_t *a, int64_t n) override { feed_search(d, a, n, nullptr); }
+
+    bool feed_scanned(const uint8_t *d, const int64_t *a, int64_t n, const uint8_t *scan) override
     {
+        feed_search(d, a, n, scan + PM_SCAN_HEAD);
+        return true;
+    }
+
+    // first set bit of the candidate bitmap at or behind byte k, n if there is none (bit k & 63 of little-endian word k >> 6)
+    static int64_t next_candidate(const uint8_t *cand, int64_t k, int64_t n)
+    {
+        while (k < n) {
+            uint64_t w;
+            memcpy(&w, cand + 8 * (k >> 6), 8);
+            w >>= k & 63;
+            if (w) return std::min<int64_t>(n, k + __builtin_ctzll(w));
+            k = (k | 63) + 1;
+        }
+        return n;
+    }
+
+    // cand: nullptr, or pm_stream_scan's bitmap of the bytes at which the sync test hits on the INPUT's last 40 bits
+    void feed_search(const uint8_t *d, const int64_t *a, int64_t n, const uint8_t *cand)
+    {
+        int64_t skipped = 0;
         for (int64_t k = 0; k < n; ++k) {
             if (state != kSync) {
                 sync_run = 0;
@@ -629,10 +697,14 @@ struct Il2p : pm_codec {
             // eight bits of it while it is inside a packet (il2p.py:146-152 with mask 0xFF) and starts with 0xFFFFFF (il2p.py:119), so
             // for the first four bytes of a sync search the register holds zeros (ones) where the input had bits, and a sync word that
             // overlaps the tail of a header or packet must be judged on the register, byte by byte, as below.
-            if (feasible && sync_run >= 4 && k >= 4 && k + 1 < n) {
+            if ((feasible || cand) && sync_run >= 4 && k >= 4 && k + 1 < n) {
                 int64_t j = k;
-                while (j < n && !feasible[((unsigned)d[j - 2] << 8) | d[j - 1]]) ++j;
+                // (with the bitmap: straight to the next byte where the test below hits -- the register IS the input's last 32 bits here,
+                // so it fails at every byte in between, and each of them would have left `word` and `nbits` as set here)
+                if (cand) j = next_candidate(cand, k, n);
+                else while (j < n && !feasible[((unsigned)d[j - 2] << 8) | d[j - 1]]) ++j;
                 if (j > k) {
+                    skipped += j - k;
                     nbits += 8 * (int)(j - k);
                     word = ((uint32_t)d[j - 4] << 24) | ((uint32_t)d[j - 3] << 16) | ((uint32_t)d[j - 2] << 8) | d[j - 1];
                     k = j;
@@ -673,6 +745,7 @@ struct Il2p : pm_codec {
             state = kHeader;
             feed_bits(b, 8 - i, a[k], sink);
         }
+        walked += n - skipped;
     }
 
     // sync_feasible(tol)[v] != 0 iff, with v as the 16 bits before the current byte, some bit offset S lets the 24-bit sync word
@@ -1090,8 +1163,31 @@ int pm_codec_decode(pm_codec *c, const uint8_t *h_data, const int64_t *h_addr, i
 {
     if (!c || n < 0 || (n > 0 && (!h_data || !h_addr)) || !h_pending)
         return pm_set_error(PM_ERR_ARG, "pm_codec_decode: bad argument");
+    c->fresh = false;
+    c->fed += n;
     c->feed_many(h_data, h_addr, n);
     *h_pending = (int64_t)c->sink.q.size();
+    return PM_OK;
+}
+
+int pm_codec_decode_scanned(pm_codec *c, const uint8_t *h_plain, const int64_t *h_addr, int64_t n, const void *h_scan, int64_t *h_pending)
+{
+    if (!c || n < 0 || (n > 0 && (!h_plain || !h_addr)) || !h_scan || !h_pending)
+        return pm_set_error(PM_ERR_ARG, "pm_codec_decode_scanned: bad argument");
+    if (!c->fresh) return pm_set_error(PM_ERR_ARG, "pm_codec_decode_scanned: the codec has been fed before (the lists are made for a just-created decoder)");
+    c->fresh = false;
+    c->fed += n;
+    if (!c->feed_scanned(h_plain, h_addr, n, static_cast<const uint8_t *>(h_scan)))
+        return pm_set_error(PM_ERR_ARG, "pm_codec_decode_scanned: the event list does not belong to a stream of %lld bytes", (long long)n);
+    *h_pending = (int64_t)c->sink.q.size();
+    return PM_OK;
+}
+
+int pm_codec_walked(pm_codec *c, int64_t *h_walked, int64_t *h_jumped)
+{
+    if (!c) return pm_set_error(PM_ERR_ARG, "pm_codec_walked: no codec");
+    if (h_walked) *h_walked = c->walked;
+    if (h_jumped) *h_jumped = c->fed - c->walked;
     return PM_OK;
 }
 
@@ -1144,13 +1240,21 @@ int pm_host_decode_batch(pm_host_job *jobs, int njobs, int threads)
         pm_host_job &q = jobs[j];
         thread_local std::vector<uint8_t> plain;
         thread_local std::vector<int64_t> wide;
-        if (!q.h_plain && (int64_t)plain.size() < q.n) plain.resize((size_t)q.n);
+        if (!q.h_plain && !q.h_scan && (int64_t)plain.size() < q.n) plain.resize((size_t)q.n);
         const int64_t *addr = q.h_addr;
         if (!addr && q.n > 0) {                 // the compact form of pm_slice_compact: first address + 16-bit steps
             if ((int64_t)wide.size() < q.n) wide.resize((size_t)q.n);
             int64_t a = q.addr_first;
             for (int64_t i = 0; i < q.n; ++i) wide[(size_t)i] = (a += q.h_addr_delta[i]);
             addr = wide.data();
+        }
+        if (q.h_scan) {                          // pm_stream_scan has descrambled: the bytes lie behind the job's list, the register in its record
+            const uint8_t *scan = static_cast<const uint8_t *>(q.h_scan);
+            const uint8_t *bytes = scan + PM_SCAN_HEAD + PM_SCAN_LIST_BYTES(q.codec->kind, q.n);
+            if (q.h_plain && q.n > 0) memcpy(q.h_plain, bytes, (size_t)q.n);
+            memcpy(&q.lfsr_state, scan, 8);
+            q.status = pm_codec_decode_scanned(q.codec, bytes, addr, q.n, scan, &q.pending);
+            return;
         }
         uint8_t *out = q.h_plain ? q.h_plain : plain.data();
         q.status = pm_lfsr_unscramble(q.h_data, q.n, q.lfsr_poly, q.lfsr_invert, &q.lfsr_state, out);

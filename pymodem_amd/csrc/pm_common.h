@@ -47,6 +47,8 @@ struct pm_tuning {
     int sweep_lds_templates = 0;       // PM_SWEEP_LDS_TEMPLATES: the fused kernel's sliding sums read their templates from LDS (as the split kernel does), not through the scalar cache
     int fused_lds_pad = 0;             // PM_FUSED_LDS_PAD: bytes of LDS the fused AFSK launch asks for beyond what it uses (12288: three workgroups per CU, 40960: two)
     int afsk_split = 0;                // PM_AFSK_SPLIT: the pipelined executor's AFSK stage as band-pass + one launch per sweep (round 4), not fused into one launch
+    int bitscan_tile_words = 0;        // PM_BITSCAN_TILE_WORDS: 64-bit words per tile of pm_stream_scan, 1 .. 256 (0: the default, 256)
+    int pipe_scan = 0;                 // PM_PIPE_SCAN: a pm_pipe made on this context runs pm_stream_scan behind its slicers and decodes from its lists
     int sweep_no_tail = 0;             // PM_SWEEP_NO_TAIL: the matrix-pipe sweep sends every uncertain sample to the list (round 4), none to its own workgroup's exact chain
 };
 pm_tuning pm_tuning_from_env();

@@ -55,6 +55,7 @@ struct Rec {                             // one recording on its way through
     // slicer output (compact form inside `block`)
     std::shared_ptr<HostBlock> block;
     std::vector<int64_t> off, count;
+    std::vector<int64_t> scan_off;                      // per chain: its part of pm_stream_scan's output inside `block` (empty: no scan)
     std::vector<std::vector<int64_t>> full_addr;        // per chain: addresses in full when a step did not fit 16 bits (else empty)
     // result
     // the packet rows: a block out of the pipeline's pool, whose rows hold zeros wherever no packet has written (RowBlock)
@@ -142,6 +143,7 @@ struct pm_pipe {
     unsigned long long *d_lists = nullptr;               // per block: nsweeps lists of kSweepCap entries (what a matrix-pipe sweep's workgroups did not decide themselves)
     std::vector<int> free_cells;
     bool keep_slices = false, trace = false;
+    bool scan = false;                   // pipe_scan of the context the pipeline was made on: pm_stream_scan behind the slicers, the host stage decodes from its lists
     bool host_copy = false;              // PM_PIPE_HOST_COPY: the slicers' compact output through a device block and a copy (round 4), not written to the host block by the kernel
     bool skip_decode = false;            // PM_PIPE_SKIP_DECODE (diagnosis only): the host stage decodes nothing -- what the GPU stages alone sustain
     int64_t next_ticket = 0, submitted = 0, finished = 0;   // submitted: tickets handed out (each is in `results` from then on)
@@ -437,11 +439,19 @@ void slice_worker(pm_pipe *p, int wi)
         const double t_b = now_ms();          // a stream with more than 1.5x its nominal symbol count: the full bound
         std::shared_ptr<HostBlock> hb;
         double t_c = t_b, t_d = t_b;
-        std::vector<int64_t> offs(jobs.size());
+        std::vector<int64_t> offs(jobs.size()), scan_offs;
         if (!rc) {
             size_t dense_cap = 0;
             for (size_t j = 0; j < caps.size(); ++j)
                 dense_cap += kCompactHead + ((size_t)2 * jobs[j].count + 7) / 8 * 8 + ((size_t)jobs[j].count + 7) / 8 * 8;
+            // (pm_stream_scan's output goes behind the compact form, into the same block: per recording and chain -- chains that share a
+            // slicer job have LFSRs and codecs of their own -- record, list and descrambled bytes, each group of 64 on a 256-byte boundary)
+            const size_t nscan = p->scan ? (size_t)nb * nch : 0;
+            for (size_t k = 0; k < nscan; ++k) {
+                const int64_t cnt = jobs[(size_t)jidx[k]].count;
+                dense_cap += PM_SCAN_HEAD + (size_t)PM_SCAN_LIST_BYTES(p->chains[k % nch].codec_kind, cnt) + ((size_t)cnt + 7) / 8 * 8;
+            }
+            dense_cap += 256 * ((nscan + 63) / 64);
             // The compact kernel writes the batch's output STRAIGHT into a page-locked host block (the device reaches it over the link:
             // hipHostMalloc memory is mapped) -- no device-side block, no copy operation behind the kernel.  As a copy of its own the
             // 8 MB took 0.2 ms in steady state but 4-12 ms whenever the demod streams had a dozen recordings queued (the first batches
@@ -485,6 +495,23 @@ void slice_worker(pm_pipe *p, int wi)
                 at += (u + 255) & ~(size_t)255;
                 used = at;
             }
+            if (!rc && nscan) {
+                std::vector<pm_scan_job> sj(nscan);
+                scan_offs.resize(nscan);
+                for (size_t k = 0; k < nscan; ++k) {
+                    const pm_pipe_chain &ch = p->chains[k % nch];
+                    const pm_slice_job &q = jobs[(size_t)jidx[k]];
+                    sj[k] = pm_scan_job{q.d_data, q.count, ch.lfsr_poly, 0, ch.lfsr_invert, ch.codec_kind, ch.sync_tol, 0};
+                }
+                for (size_t j0 = 0; j0 < nscan && !rc; j0 += 64) {
+                    const int nj = (int)std::min<size_t>(64, nscan - j0);
+                    size_t u = 0;
+                    rc = pm_stream_scan(side, sj.data() + j0, nj, dst + at, dst_bytes - at, scan_offs.data() + j0, &u);
+                    for (int k = 0; k < nj; ++k) scan_offs[j0 + k] += (int64_t)at;
+                    at += (u + 255) & ~(size_t)255;
+                    used = at;
+                }
+            }
             t_d = now_ms();
             if (!rc && !direct && hipMemcpyAsync(hb->p, w.d_dense, used, hipMemcpyDeviceToHost, side->stream) != hipSuccess) rc = pm_set_error(PM_ERR_HIP, "copy of the slicer output failed");
             if (!rc && hipStreamSynchronize(side->stream) != hipSuccess) rc = pm_set_error(PM_ERR_HIP, "slicer stream failed");
@@ -503,6 +530,7 @@ void slice_worker(pm_pipe *p, int wi)
                 r.off.assign(nch, 0);
                 r.count.assign(nch, 0);
                 r.full_addr.assign(nch, {});
+                if (!scan_offs.empty()) r.scan_off.assign(scan_offs.begin() + (ptrdiff_t)b * nch, scan_offs.begin() + (ptrdiff_t)(b + 1) * nch);
                 for (int c = 0; c < nch && !r.status; ++c) {
                     const size_t j = (size_t)jidx[(size_t)b * nch + c];
                     r.off[c] = offs[j];
@@ -579,6 +607,7 @@ void host_worker(pm_pipe *p)
                 j.lfsr_poly = ch.lfsr_poly;
                 j.lfsr_state = 0;
                 j.lfsr_invert = ch.lfsr_invert;
+                if (!r.scan_off.empty() && !p->skip_decode) j.h_scan = r.block->p + r.scan_off[c];
             }
             if (!rc && p->keep_slices) {
                 // the slicer's output as it reached the host, addresses in full, and room for the LFSR's bytes (pm_host_job.h_plain)
@@ -718,6 +747,7 @@ int pm_pipe_create(pm_ctx *ctx, const pm_pipe_desc *desc, pm_pipe **out)
     const int nd = d.demod_streams > 0 ? std::min(d.demod_streams, 4) : 2;
     p->slots = std::max(2, p->slots);
     p->keep_slices = d.keep_slices != 0;
+    p->scan = ctx->tune.pipe_scan != 0;
     p->trace = getenv("PM_PIPE_TRACE") != nullptr;
     p->skip_decode = getenv("PM_PIPE_SKIP_DECODE") != nullptr;
     p->host_copy = getenv("PM_PIPE_HOST_COPY") != nullptr;
@@ -874,6 +904,7 @@ int pm_pipe_create(pm_ctx *ctx, const pm_pipe_desc *desc, pm_pipe **out)
             // third of the whole GPU's time per recording)
             if (!(rc = pm_ctx_create_prio(ctx->device, 1, &s))) {
                 p->side.push_back(s);
+                s->tune.bitscan_tile_words = ctx->tune.bitscan_tile_words;
                 rc = pm_slicer_tune(s, 16384);
                 // walkers of 32 k samples: the slicers are a third of the GPU's work now, and a walker re-walks its merge length
                 // (10-20 k samples) whatever the chunk -- 1 + m/L lane-steps per sample; longer chunks cost depth, not work

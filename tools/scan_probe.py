@@ -1,0 +1,44 @@
+"""pm_stream_scan on its own, for a kernel trace: a slicer batch's worth of streams of fsk_9600's size (four recordings x three chains,
+0.45 MB of slicer bytes each: IL2P plain and inverted, G3RUH AX.25), random bytes, `reps` calls behind each other.
+    rocprofv3 --kernel-trace --stats -d <dir> -- python tools/scan_probe.py [reps]"""
+import ctypes
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import pymodem_amd                                                    # noqa: E402
+from pymodem_amd._native import SCAN_HEAD, ScanJob, check, lib, scan_list_bytes      # noqa: E402
+
+
+def main():
+    reps = int(sys.argv[1]) if len(sys.argv) > 1 else 50
+    ctx = pymodem_amd.Context.default()
+    n = 450_000
+    chains = [(0x1, 0, 1), (0x1, 1, 1), (0x63003, 1, 0)]           # (poly, invert, codec kind) of configs/fsk_9600.json
+    rng = np.random.default_rng(1)
+    bufs = [ctx.upload(rng.integers(0, 256, n, dtype=np.uint8)) for _ in range(4 * len(chains))]
+    jobs = (ScanJob * len(bufs))()
+    need = 0
+    for k, (q, b) in enumerate(zip(jobs, bufs)):
+        poly, inv, kind = chains[k % len(chains)]
+        q.d_data, q.n, q.lfsr_poly, q.lfsr_state, q.lfsr_invert, q.codec_kind, q.sync_tol = b.ptr.value, n, poly, 0, inv, kind, 2
+        need += SCAN_HEAD + scan_list_bytes(kind, n) + (n + 7) // 8 * 8
+    block = ctx.empty(need, np.uint8)
+    offs, used = (ctypes.c_int64 * len(bufs))(), ctypes.c_size_t()
+    for timed in (False, True):
+        ctx.sync()
+        t0 = time.perf_counter()
+        for _ in range(reps if timed else 3):
+            check(lib().pm_stream_scan(ctx.handle, jobs, len(bufs), block.ptr, need, offs, ctypes.byref(used)))
+        ctx.sync()
+        if timed:
+            ms = (time.perf_counter() - t0) * 1e3 / reps
+            print(f"pm_stream_scan: {len(bufs)} streams x {n} bytes, {ms:.3f} ms per call (host clock around {reps} calls and a stream wait), "
+                  f"{len(bufs) * n / ms / 1e6:.1f} GB/s of slicer bytes")
+
+
+if __name__ == "__main__":
+    main()
