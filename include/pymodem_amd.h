@@ -384,10 +384,24 @@ int pm_slice_compact(pm_ctx *ctx, const pm_slice_job *h_jobs, int njobs, void *d
  *               one of byte k's eight bits, 24 bits within sync_tol of 0xF15E48 or 32 bits within sync_tol of 0x5D57DF7F
  *       kind -1: nothing
  *   the n descrambled bytes, padded with zeros to a multiple of 8.
+ * With pm_scan_job.frames = 1 (kind 0 only; PM_ERR_ARG otherwise) two more pieces follow, for pm_codec_decode_framed:
+ *   the frame table, PM_SCAN_FRAME_TABLE_BYTES(n): n / 19 + 2 places of 8 bytes parallel to the list, the first `events` of them
+ *       {int32 len, uint32 crc}: the frame that the flag at P closes in a decoder that starts, with everything cleared, at F (at bit 0 when
+ *       F is none) -- a zero behind exactly five ones dropped; the seventh one of a run and every one after it clear the bit and byte
+ *       counters and the zero that ends the run is not appended, the bytes collected so far stay; every other bit appended, eight appended
+ *       bits since the counters were last clear a byte, the first in bit 0.  len: all its bytes (it may exceed PM_PKT_MAX), 0: the flag
+ *       closes nothing (the stream's first flag only); crc: pm_crc16_ccitt of the frame less its last two bytes.  Places past `events`
+ *       are not written.
+ *   the frame area, PM_SCAN_FRAME_AREA_BYTES(n): frame e lies at byte max(F, 0) >> 3 (it ends in front of byte (P >> 3) + 1, so frames
+ *       do not overlap); bytes that no frame covers are not written.
+ * One more launch, a wave per event, pm_ctx_tune(ctx, "bitscan_frame_words", 1 .. 64) words of the span per trip (0: 64); results do
+ * not depend on it.
  * *h_used = bytes the batch needs; PM_ERR_CAPACITY (with *h_used set) if block_bytes is less.  n <= 2^29, njobs <= 64.  Tiles of
  * pm_ctx_tune(ctx, "bitscan_tile_words", 1 .. 256) 64-bit words (0: the default, 256); results do not depend on it. */
 #define PM_SCAN_HEAD 32
 #define PM_SCAN_LIST_BYTES(kind, n) ((kind) == 0 ? 8 * ((n) / 19 + 2) : (kind) == 1 ? 8 * (((n) + 63) / 64) : 0)     /* the list's bytes: the descrambled bytes lie behind it */
+#define PM_SCAN_FRAME_TABLE_BYTES(n) (8 * ((n) / 19 + 2))       /* frames: behind the descrambled bytes (padded to 8) ... */
+#define PM_SCAN_FRAME_AREA_BYTES(n) (((n) + 7) / 8 * 8)         /* ... and behind the table */
 typedef struct pm_scan_job {
     const uint8_t *d_data;
     int64_t n;
@@ -396,7 +410,7 @@ typedef struct pm_scan_job {
     int32_t lfsr_invert;
     int32_t codec_kind;              /* 0 AX.25, 1 IL2P, -1 none */
     int32_t sync_tol;
-    int32_t reserved;
+    int32_t frames;                  /* 1 (kind 0 only): the frame table and the frame area behind the descrambled bytes */
 } pm_scan_job;
 int pm_stream_scan(pm_ctx *ctx, const pm_scan_job *h_jobs, int njobs, void *d_block, size_t block_bytes, int64_t *h_offsets, size_t *h_used);
 /* How many chunks (= walkers) a batch is cut into on this ctx, within 1024..16384 samples per chunk; 0 restores the default 16384.
@@ -560,6 +574,11 @@ int pm_codec_fetch(pm_codec *c, pm_packet *h_out, int64_t cap, int64_t *h_count)
  * from the event list instead of searching for them, IL2P jumps from sync candidate to sync candidate of the bitmap instead of testing
  * every byte; packets, *h_pending and the state the decoder is left in are pm_codec_decode's. */
 int pm_codec_decode_scanned(pm_codec *c, const uint8_t *h_plain, const int64_t *h_addr, int64_t n, const void *h_scan, int64_t *h_pending);
+/* The same for an AX.25 codec and a block made with pm_scan_job.frames: every listed flag's frame is taken from the frame area as it is
+ * (address h_addr[P >> 3], the table's CRC as the calculated one) and nothing in front of the stream's last flag goes through the decoder;
+ * from there to the end it decodes byte by byte, which leaves the registers as pm_codec_decode would and finds what lies behind a bail.
+ * PM_ERR_ARG for a table that cannot belong to the stream (len < 0, more bytes than the span from F to P holds, a frame past byte n). */
+int pm_codec_decode_framed(pm_codec *c, const uint8_t *h_plain, const int64_t *h_addr, int64_t n, const void *h_scan, int64_t *h_pending);
 /* Bytes this codec has taken through its byte-by-byte machine so far, and bytes it has passed over (either may be NULL). */
 int pm_codec_walked(pm_codec *c, int64_t *h_walked, int64_t *h_jumped);
 
@@ -585,6 +604,7 @@ typedef struct pm_host_job {
     const void *h_scan;           /* NULL, or the job's part of a pm_stream_scan block (record, list, bytes), made from the same */
                                   /* h_data, LFSR and codec kind: the descrambled bytes and the register come from there and the */
                                   /* codec goes through pm_codec_decode_scanned (h_plain, if given, receives a copy of the bytes) */
+    int32_t scan_frames;          /* with h_scan, AX.25 codecs only: the block was made with pm_scan_job.frames -> pm_codec_decode_framed */
 } pm_host_job;
 int pm_host_decode_batch(pm_host_job *jobs, int njobs, int threads);
 int pm_codec_fetch_batch(pm_codec *const *codecs, const int64_t *counts, int n, pm_packet *h_out, int threads);
@@ -627,6 +647,8 @@ int64_t pm_correlate_strided(void *h_records, int64_t stride, const int64_t *h_c
  *                    pm_pipe_release
  * With the context's switch pipe_scan (pm_ctx_tune, PM_PIPE_SCAN; read by pm_pipe_create, default 0) the slicer threads run pm_stream_scan
  * behind pm_slice_compact, into the same block, and the host threads decode from its lists (pm_host_job.h_scan); results are the same.
+ * The switch pipe_frames (PM_PIPE_FRAMES, default 0) implies pipe_scan and has the AX.25 chains' jobs write their frames too
+ * (pm_scan_job.frames, pm_host_job.scan_frames); IL2P chains go the pipe_scan way.
  * Results equal process_chain on every chain + PacketMetaArray.Correlate, recording by recording.  One submitting thread.  The
  * device pointers inside the descs (taps) must stay valid for the pipeline's life; host arrays are copied by pm_pipe_create. */
 typedef struct pm_pipe_fir {         /* a sign-FIR group: sign(FIR(int16 audio)) as one bitmap (pm_fir_signs_i16) -- FSKModem.demod, fsk.py:149-159 */

@@ -85,13 +85,13 @@ class HostJob(ctypes.Structure):
                 ("lfsr_poly", ctypes.c_uint64), ("lfsr_state", ctypes.c_uint64), ("pending", ctypes.c_int64),
                 ("lfsr_invert", ctypes.c_int32), ("status", ctypes.c_int32),
                 ("h_addr_delta", ctypes.c_void_p), ("addr_first", ctypes.c_int64), ("h_plain", ctypes.c_void_p),
-                ("h_scan", ctypes.c_void_p)]
+                ("h_scan", ctypes.c_void_p), ("scan_frames", ctypes.c_int32)]
 
 
 class ScanJob(ctypes.Structure):
     """pm_scan_job"""
     _fields_ = [("d_data", ctypes.c_void_p), ("n", ctypes.c_int64), ("lfsr_poly", ctypes.c_uint64), ("lfsr_state", ctypes.c_uint64),
-                ("lfsr_invert", ctypes.c_int32), ("codec_kind", ctypes.c_int32), ("sync_tol", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+                ("lfsr_invert", ctypes.c_int32), ("codec_kind", ctypes.c_int32), ("sync_tol", ctypes.c_int32), ("frames", ctypes.c_int32)]
 
 
 SCAN_HEAD = 32        # PM_SCAN_HEAD
@@ -100,6 +100,16 @@ SCAN_HEAD = 32        # PM_SCAN_HEAD
 def scan_list_bytes(kind, n):
     """PM_SCAN_LIST_BYTES: the bytes of a job's list inside a pm_stream_scan block (the descrambled bytes lie behind it)."""
     return 8 * (n // 19 + 2) if kind == 0 else 8 * ((n + 63) // 64) if kind == 1 else 0
+
+
+def scan_frame_table_bytes(n):
+    """PM_SCAN_FRAME_TABLE_BYTES: the frame table of a job with `frames` set, behind its descrambled bytes (padded to 8)."""
+    return 8 * (n // 19 + 2)
+
+
+def scan_frame_area_bytes(n):
+    """PM_SCAN_FRAME_AREA_BYTES: the frame area, behind the table."""
+    return (n + 7) // 8 * 8
 
 
 def scan_record_dtype():
@@ -308,6 +318,7 @@ _SIGS = {
     "pm_codec_set_source": ([_vp, ctypes.c_int32], _int),
     "pm_codec_decode": ([_vp, _vp, _vp, _i64, ctypes.POINTER(_i64)], _int),
     "pm_codec_decode_scanned": ([_vp, _vp, _vp, _i64, _vp, ctypes.POINTER(_i64)], _int),
+    "pm_codec_decode_framed": ([_vp, _vp, _vp, _i64, _vp, ctypes.POINTER(_i64)], _int),
     "pm_codec_walked": ([_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)], _int),
     "pm_codec_fetch": ([_vp, _vp, _i64, ctypes.POINTER(_i64)], _int),
     "pm_host_decode_batch": ([ctypes.POINTER(HostJob), _int, _int], _int),

@@ -846,7 +846,7 @@ class NativePipeline:
     raises ValueError for anything else (use RecordingPipeline there)."""
 
     def __init__(self, chains, max_samples, address_distance, ctx=None, names=None, chain_ids=None, slots=0, slice_workers=0, slice_group=0,
-                 host_threads=0, decode_threads=0, slice_min_group=0, demod_streams=0, keep_slices=False, scan=False):
+                 host_threads=0, decode_threads=0, slice_min_group=0, demod_streams=0, keep_slices=False, scan=False, frames=False):
         import os
         demod_streams = demod_streams or int(os.environ.get("PYMODEM_AMD_PIPE_DEMOD_STREAMS", 0))
         slots = slots or int(os.environ.get("PYMODEM_AMD_PIPE_SLOTS", 0))              # tuning knobs (DESIGN.md 4.4b)
@@ -924,15 +924,15 @@ class NativePipeline:
         desc.keep_slices = int(bool(keep_slices))
         h = ctypes.c_void_p()
         # scan: the bitstream stage on the device (pm_stream_scan behind the slicers, the codecs decode from its lists).  pm_pipe_create
-        # reads the switch from its context
-        if scan:
-            ctx.tune(pipe_scan=1)
+        # reads the switch from its context.  frames: that, and the AX.25 chains' frames (de-stuffed bytes and CRC) come from the device too
+        on = {k: 1 for k, v in (("pipe_scan", scan), ("pipe_frames", frames)) if v}
+        ctx.tune(**on)
         try:
             check(lib().pm_pipe_create(ctx.handle, ctypes.byref(desc), ctypes.byref(h)))
         finally:
-            if scan:                                        # back to what the context read when it was made
-                e = os.environ.get("PM_PIPE_SCAN")
-                ctx.tune(pipe_scan=0 if e is None else int(e) if e.lstrip("-").isdigit() else 1)
+            for k in on:                                    # back to what the context read when it was made
+                e = os.environ.get("PM_" + k.upper())
+                ctx.tune(**{k: 0 if e is None else int(e) if e.lstrip("-").isdigit() else 1})
         self._h = h
         self.nchains = n
         self.done_at_ms = {}                                # ticket -> when it left the last stage (host clock since the pipeline was made)

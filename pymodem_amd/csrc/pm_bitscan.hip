@@ -9,7 +9,10 @@
 // launch writes the list.  No workgroup waits for another inside a launch; every write is a plain store at a place that follows from
 // prefix counts, so the lists come out sorted and nothing has to be cleared beforehand.
 // Bits are handled in STREAM order: bit i of a word is stream bit 64 w + i (the bytes' bits from the top, as the slicer packs them).
+// With pm_scan_job.frames a fourth launch writes, for every listed flag, the frame it closes -- the de-stuffed bytes the decoder would have
+// collected since the flag in front, and their CRC-16 -- a wave per event, from a copy of the list that the emit launch leaves on the device.
 #include "pm_common.h"
+#include "pm_bitscan_frames.h"
 #include <algorithm>
 #include <cstring>
 
@@ -28,7 +31,11 @@ struct ScanJobs {
     int32_t tile0[kScanJobs + 1];           // first tile of the job among the batch's
     int8_t kind[kScanJobs], invert[kScanJobs], tol[kScanJobs];
     int32_t njobs, tile_words;
+    int64_t ev0[kScanJobs];                 // frames: the job's first place in the device-side copy of the lists, -1: no frames
+    int32_t frame_words;
 };
+constexpr int kFrameWaves = 256;            // waves that share a job's events in the frames launch (a wave a workgroup: the others leave at once)
+constexpr uint32_t kClosesNothing = 0xFFFFFFFEu;   // F of the stream's first flag in the device-side copy when no frame ends there
 
 // One tile as the tiles in front of it see it.  Positions are bits from the tile's start, -1: none.  Events at or behind `bail` (the
 // first event of the tile whose span since a reset INSIDE the tile reaches kBailSpan) are left out of last_flag, first_flag and closing.
@@ -285,7 +292,7 @@ __global__ __launch_bounds__(kLanes) void bitscan_tile_kernel(ScanJobs J, uint8_
 }
 
 // Launch 2: a wave per stream takes the summaries in order, 64 at a time (a lane loads one, all lanes step through them together).
-__global__ __launch_bounds__(64) void bitscan_combine_kernel(ScanJobs J, uint8_t *block, const TileSum *sums, TileCarry *carries)
+__global__ __launch_bounds__(64) void bitscan_combine_kernel(ScanJobs J, uint8_t *block, const TileSum *sums, TileCarry *carries, int32_t *counts)
 {
     const int j = blockIdx.x, lane = threadIdx.x, tw = J.tile_words;
     const int t0 = J.tile0[j], nt = J.tile0[j + 1] - t0;
@@ -343,11 +350,12 @@ __global__ __launch_bounds__(64) void bitscan_combine_kernel(ScanJobs J, uint8_t
         *reinterpret_cast<int64_t *>(rec + 16) = kind == 0 ? LF : -1;
         *reinterpret_cast<int32_t *>(rec + 24) = kind == 0 ? events : 0;
         *reinterpret_cast<int32_t *>(rec + 28) = kind == 1 ? cands : 0;
+        if (counts) counts[j] = kind == 0 ? events : 0;      // for the frames launch: the block may be host memory, nothing is read back from it
     }
 }
 
 // Launch 3: the events of every AX.25 tile, at the places the combine counted out.
-__global__ __launch_bounds__(kLanes) void bitscan_emit_kernel(ScanJobs J, uint8_t *block, const TileCarry *carries)
+__global__ __launch_bounds__(kLanes) void bitscan_emit_kernel(ScanJobs J, uint8_t *block, const TileCarry *carries, uint2 *copies)
 {
     __shared__ Seg lds[kLanes];
     __shared__ int32_t cnt[kLanes];
@@ -372,14 +380,17 @@ __global__ __launch_bounds__(kLanes) void bitscan_emit_kernel(ScanJobs J, uint8_
     const int64_t limit = c.bail >= 0 ? c.bail : INT64_MAX;
     // a closing flag has 151 counted bits behind it: a word holds one at most, and the stream's first flag beside it
     uint2 found[2];
-    int nfound = 0;
+    int nfound = 0, nothing = 0;                            // nothing: bit k set when found[k] closes no frame (the stream's first flag only)
     walk_events(in, [&](int32_t P, bool is_flag, int32_t R, int32_t dropped, int32_t F) {
         const int64_t Pa = B + P;
         if (Pa >= limit) return false;
         if (!is_flag) return true;
         const int64_t T = R >= 0 ? (int64_t)(P - R) - dropped : (Pa - c.after_reset) - ((int64_t)c.dropped + dropped);
         const int64_t Fa = F >= 0 ? B + F : c.after_flag;
-        if ((Fa < 0 || closes(T)) && nfound < 2) found[nfound++] = make_uint2((uint32_t)Pa, (uint32_t)Fa);
+        if ((Fa < 0 || closes(T)) && nfound < 2) {
+            if (!closes(T)) nothing |= 1 << nfound;
+            found[nfound++] = make_uint2((uint32_t)Pa, (uint32_t)Fa);
+        }
         return true;
     });
     block_scan((int32_t)nfound, cnt, [](int32_t a, int32_t b) { return a + b; });
@@ -387,6 +398,137 @@ __global__ __launch_bounds__(kLanes) void bitscan_emit_kernel(ScanJobs J, uint8_
     uint2 *events = reinterpret_cast<uint2 *>(block + J.off[j] + PM_SCAN_HEAD);
     for (int k = 0; k < nfound; ++k)
         if (at + k < cap) events[at + k] = found[k];
+    if (J.ev0[j] >= 0)
+        for (int k = 0; k < nfound; ++k)
+            if (at + k < cap) copies[J.ev0[j] + at + k] = make_uint2(found[k].x, (nothing >> k) & 1 ? kClosesNothing : found[k].y);
+}
+
+// Launch 4 (pm_scan_job.frames): a wave per listed flag {P, F} -- the events e, e + waves, ... of its job, the count read from the combine
+// launch's device-side copy -- writes the frame that ends there.  The span from F (or the stream's start) to P is taken `frame_words`
+// words per trip, a lane a word: the lane's word as the counters see it (pm_bitscan_frames.h), a scan over the lanes for the counters in
+// front of each word, the word's appended bits squeezed together and ORed into a line in LDS at the place their byte has in the frame, the
+// line's whole bytes out to the frame area, the CRC continued over them, a lane a piece.  The line is laid out so that its 8-byte words are
+// the area's: whole words go out as one store, the bytes at a frame's two ends one by one (the neighbouring frames' bytes share those
+// words).  Up to seven bits of a byte that the trip leaves unfinished stay in the line for the next trip.
+__global__ __launch_bounds__(64) void bitscan_frames_kernel(ScanJobs J, uint8_t *block, const uint2 *copies, const int32_t *counts)
+{
+    using namespace pm_frames;
+    constexpr int kLineWords = 136;                         // 7 bytes of alignment, 7 bits left over, 64 words of 64 bits, and the OR's reach
+    __shared__ uint32_t line[kLineWords];
+    __shared__ uint16_t crc_table[256];
+    const int j = blockIdx.y, lane = threadIdx.x;
+    if (J.ev0[j] < 0) return;
+    const int64_t n = J.n[j], cap = n / 19 + 2;
+    const int32_t count = (int32_t)(counts[j] < cap ? counts[j] : cap);
+    if ((int)blockIdx.x >= count) return;
+    for (int v = lane; v < 256; v += 64) {
+        unsigned c = (unsigned)v;
+        for (int i = 0; i < 8; ++i) c = (c & 1) ? (c >> 1) ^ 0x8408u : c >> 1;      // crc_functions.py:44-55, eight bits at a time
+        crc_table[v] = (uint16_t)c;
+    }
+    const uint8_t *d = J.data[j];
+    uint8_t *table = block + J.off[j] + PM_SCAN_HEAD + list_bytes(0, n) + ((n + 7) & ~int64_t(7)), *area = table + PM_SCAN_FRAME_TABLE_BYTES(n);
+    const int fw = J.frame_words;
+    auto or_word = [&](int at, uint32_t v) { atomicOr(&line[at], v); };
+    for (int32_t e = (int32_t)blockIdx.x; e < count; e += (int32_t)gridDim.x) {
+        const uint2 pf = copies[J.ev0[j] + e];
+        const int64_t P = pf.x, s = pf.y >= kClosesNothing ? 0 : (int64_t)pf.y;
+        if (pf.y == kClosesNothing || P >= 8 * n || s >= P) {
+            if (lane == 0) *reinterpret_cast<uint2 *>(table + 8 * (int64_t)e) = make_uint2(0u, 0u);
+            continue;
+        }
+        const int64_t w_first = s >> 6, w_last = (P - 1) >> 6, at0 = s >> 3;        // at0: the frame's first byte in the area
+        State carry{0, 0};                                  // the counters in front of the trip
+        int64_t out = 0;                                    // bytes of the frame that have gone out: carry.bytes + carry.open / 8
+        uint32_t left = 0;                                  // the carry.open % 8 bits of the unfinished byte
+        uint32_t crc = 0xFFFF, held0 = 0, held1 = 0;        // the CRC's register for the frame less its last two bytes, which are held back
+        for (int64_t wt = w_first; wt <= w_last; wt += fw) {
+            const int64_t w = wt + lane;
+            const bool active = lane < fw && w <= w_last;
+            uint64_t x = 0;
+            WordMarks k{0, 0};
+            if (active) {
+                const uint64_t i0 = load_word(d, n, w), i1 = load_word(d, n, w - 1), i2 = load_word(d, n, w - 2);
+                x = plain_word(J, j, w, i0, i1);
+                const uint64_t xp = w ? plain_word(J, j, w - 1, i1, i2) : 0;
+                const uint64_t span = low_mask(w == w_last ? (int)((P - 1) & 63) + 1 : 64) & ~low_mask(w == w_first ? (int)(s & 63) : 0);
+                k = word_marks(x, xp, span);
+            }
+            const Span mine = active ? word_span(k) : Span{0, 0, 0, 0};
+            Span upto = mine;                               // inclusive over the lanes
+            for (int dl = 1; dl < 64; dl <<= 1) {
+                Span o{__shfl_up(upto.r, dl), __shfl_up(upto.a, dl), __shfl_up(upto.m, dl), __shfl_up(upto.t, dl)};
+                if (lane >= dl) upto = join(o, upto);
+            }
+            Span before{__shfl_up(upto.r, 1), __shfl_up(upto.a, 1), __shfl_up(upto.m, 1), __shfl_up(upto.t, 1)};
+            if (lane == 0) before = Span{0, 0, 0, 0};
+            const Span all{__shfl(upto.r, 63), __shfl(upto.a, 63), __shfl(upto.m, 63), __shfl(upto.t, 63)};
+            const State st = advance(carry, before), next = advance(carry, all);
+            // what the segment open behind a word has when it closes: the lane of the next reset knows
+            const uint64_t resets = __ballot(mine.r != 0);
+            const int32_t closes_at = st.open + mine.a;
+            const uint64_t behind = lane < 63 ? resets & ~low_mask(lane + 1) : 0;
+            const int32_t from_next = __shfl(closes_at, behind ? __builtin_ctzll(behind) : lane);
+            const int32_t later = behind ? from_next : kOpenEnded;
+            const int32_t head = __shfl(closes_at, resets ? __builtin_ctzll(resets) : 0);
+            const int sh = (int)((at0 + out) & 7);          // the line's byte sh is the frame's byte `out`
+            __syncthreads();
+            for (int v = lane; v < kLineWords; v += 64) line[v] = 0;
+            __syncthreads();
+            // the unfinished byte is the frame's if its segment gets that far; otherwise the next segment's first byte takes its place
+            if (lane == 0 && left && !(resets && (head >> 3) == (carry.open >> 3))) line[sh >> 2] = left << (8 * (sh & 3));
+            __syncthreads();
+            if (active) put_word(x, k, st, 8 * ((int64_t)sh - out), later, or_word);
+            __syncthreads();
+            const int64_t total = next.bytes + (next.open >> 3);
+            const int nb = (int)(total - out);              // whole bytes of this trip: the line's bytes sh .. sh + nb
+            // the CRC runs two bytes behind the frame: over this trip's bytes but the last two, behind the two held back from the trip before
+            {
+                const int64_t lo = out > 2 ? out - 2 : 0, hi = total > 2 ? total - 2 : 0;
+                const int len = (int)(hi - lo), old = (int)(out - lo);            // old: how many of them are held-back bytes
+                auto byte = [&](int k) -> uint32_t {
+                    if (k < old) return k + 2 - old ? held1 : held0;
+                    const int q = sh + (k - old);
+                    return (line[q >> 2] >> (8 * (q & 3))) & 0xFF;
+                };
+                if (len == 1) {
+                    crc = (crc >> 8) ^ crc_table[(crc ^ byte(0)) & 0xFF];
+                } else if (len >= 2) {
+                    const int per = (len + 63) >> 6;
+                    uint32_t piece = crc_piece(crc_table, lane, len, per, crc, byte), f = crc_times_x(0x8000u, 8 * per);
+                    for (int dl = 1; dl < 64; dl <<= 1) {
+                        const uint32_t o = __shfl_up(piece, dl);
+                        if (lane >= dl) piece ^= crc_mul(f, o);
+                        f = crc_mul(f, f);
+                    }
+                    crc = __shfl(piece, 63);
+                }
+                if (nb >= 2) {
+                    held0 = (line[(sh + nb - 2) >> 2] >> (8 * ((sh + nb - 2) & 3))) & 0xFF;
+                    held1 = (line[(sh + nb - 1) >> 2] >> (8 * ((sh + nb - 1) & 3))) & 0xFF;
+                } else if (nb == 1) {
+                    held0 = held1;
+                    held1 = (line[sh >> 2] >> (8 * (sh & 3))) & 0xFF;
+                }
+            }
+            uint8_t *dst = area + at0 + out - sh;           // 8-byte aligned: the line's byte 0
+            for (int q0 = 8 * lane; q0 < sh + nb; q0 += 512) {
+                const uint64_t v = line[q0 >> 2] | (uint64_t)line[(q0 >> 2) + 1] << 32;
+                if (q0 >= sh && q0 + 8 <= sh + nb) {
+                    *reinterpret_cast<uint64_t *>(dst + q0) = v;
+                } else {
+                    for (int q = q0 > sh ? q0 : sh; q < q0 + 8 && q < sh + nb; ++q) dst[q] = (uint8_t)(v >> (8 * (q - q0)));
+                }
+            }
+            const int qe = sh + nb;
+            left = (line[qe >> 2] >> (8 * (qe & 3))) & 0xFF & (uint32_t)low_mask(next.open & 7);
+            out = total;
+            carry = next;
+        }
+        // the flag closes a frame when the last segment holds 18 bytes or more and the flag's own seven bits (ax25.py:74-81)
+        const bool closing = (carry.open & 7) == 7 && carry.open >= kCloseBits;
+        if (lane == 0) *reinterpret_cast<uint2 *>(table + 8 * (int64_t)e) = closing ? make_uint2((uint32_t)out, (crc ^ 0xFFFF) & 0xFFFF) : make_uint2(0u, 0u);
+    }
 }
 
 }  // namespace
@@ -400,12 +542,15 @@ extern "C" int pm_stream_scan(pm_ctx *ctx, const pm_scan_job *h_jobs, int njobs,
     J.njobs = njobs;
     const int tune = ctx->tune.bitscan_tile_words;
     J.tile_words = tune > 0 ? std::min(tune, kLanes) : kLanes;
+    const int ftune = ctx->tune.bitscan_frame_words;
+    J.frame_words = ftune > 0 ? std::min(ftune, 64) : 64;
     size_t at = 0;
-    int64_t tiles = 0;
+    int64_t tiles = 0, copies = 0;
     for (int j = 0; j < njobs; ++j) {
         const pm_scan_job &q = h_jobs[j];
         PM_ARG(q.n >= 0 && q.n <= (int64_t)1 << 29 && (q.n == 0 || (q.d_data && ((uintptr_t)q.d_data & 7) == 0)));
         PM_ARG(q.codec_kind >= -1 && q.codec_kind <= 1);
+        PM_ARG(q.frames == 0 || (q.frames == 1 && q.codec_kind == 0));
         J.data[j] = q.d_data;
         J.poly[j] = q.lfsr_poly;
         J.reg0[j] = q.lfsr_state;
@@ -416,6 +561,12 @@ extern "C" int pm_stream_scan(pm_ctx *ctx, const pm_scan_job *h_jobs, int njobs,
         J.off[j] = h_offsets[j] = (int64_t)at;
         J.tile0[j] = (int32_t)tiles;
         at += PM_SCAN_HEAD + (size_t)list_bytes(q.codec_kind, q.n) + (size_t)((q.n + 7) & ~int64_t(7));
+        J.ev0[j] = -1;
+        if (q.frames) {
+            at += (size_t)PM_SCAN_FRAME_TABLE_BYTES(q.n) + (size_t)PM_SCAN_FRAME_AREA_BYTES(q.n);
+            J.ev0[j] = copies;
+            copies += q.n / 19 + 2;
+        }
         tiles += pm_cdiv(pm_cdiv(q.n, 8), J.tile_words);
         PM_ARG(tiles < (int64_t)1 << 30);
     }
@@ -423,15 +574,20 @@ extern "C" int pm_stream_scan(pm_ctx *ctx, const pm_scan_job *h_jobs, int njobs,
     *h_used = at;
     if (at > block_bytes) return pm_set_error(PM_ERR_CAPACITY, "pm_stream_scan: the block holds %zu bytes, the batch needs %zu", block_bytes, at);
     const size_t sums_bytes = ((size_t)tiles * sizeof(TileSum) + 63) & ~(size_t)63;
-    if (int rc = pm_scratch_reserve(ctx, sums_bytes + (size_t)tiles * sizeof(TileCarry) + 64)) return rc;
+    // (frames: the event counts and a copy of the lists stay on the device for the frames launch, behind the carries)
+    const size_t carries_bytes = ((size_t)tiles * sizeof(TileCarry) + 63) & ~(size_t)63, counts_bytes = copies ? kScanJobs * sizeof(int32_t) : 0;
+    if (int rc = pm_scratch_reserve(ctx, sums_bytes + carries_bytes + counts_bytes + (size_t)copies * sizeof(uint2) + 64)) return rc;
     TileSum *sums = static_cast<TileSum *>(ctx->d_scratch);
     TileCarry *carries = reinterpret_cast<TileCarry *>(static_cast<uint8_t *>(ctx->d_scratch) + sums_bytes);
+    int32_t *counts = copies ? reinterpret_cast<int32_t *>(static_cast<uint8_t *>(ctx->d_scratch) + sums_bytes + carries_bytes) : nullptr;
+    uint2 *lists = reinterpret_cast<uint2 *>(static_cast<uint8_t *>(ctx->d_scratch) + sums_bytes + carries_bytes + counts_bytes);
     uint8_t *block = static_cast<uint8_t *>(d_block);
     if (tiles) hipLaunchKernelGGL(bitscan_tile_kernel, dim3((unsigned)tiles), dim3(kLanes), 0, ctx->stream, J, block, sums);
-    hipLaunchKernelGGL(bitscan_combine_kernel, dim3(njobs), dim3(64), 0, ctx->stream, J, block, sums, carries);
+    hipLaunchKernelGGL(bitscan_combine_kernel, dim3(njobs), dim3(64), 0, ctx->stream, J, block, sums, carries, counts);
     bool any = false;
     for (int j = 0; j < njobs; ++j) any = any || (h_jobs[j].codec_kind == 0 && h_jobs[j].n > 0);
-    if (any) hipLaunchKernelGGL(bitscan_emit_kernel, dim3((unsigned)tiles), dim3(kLanes), 0, ctx->stream, J, block, carries);
+    if (any) hipLaunchKernelGGL(bitscan_emit_kernel, dim3((unsigned)tiles), dim3(kLanes), 0, ctx->stream, J, block, carries, lists);
+    if (copies) hipLaunchKernelGGL(bitscan_frames_kernel, dim3(kFrameWaves, njobs), dim3(64), 0, ctx->stream, J, block, lists, counts);
     PM_HIP(hipGetLastError());
     return PM_OK;
 }

@@ -61,11 +61,12 @@ bool valid_header(const uint8_t *d, int len)
     return true;
 }
 
-void finalize(pm_packet &p)
+// crc: the frame's calculated CRC if whoever queued it knows it (pm_stream_scan's frame table), -1: computed here
+void finalize(pm_packet &p, int crc = -1)
 {
     // PacketMeta.CalcCRC / Validate, packet_meta.py:197-208 (needs len >= 2, which every emitter guarantees)
     p.carried_crc = p.len >= 2 ? p.data[p.len - 1] * 256 + p.data[p.len - 2] : 0;
-    p.calculated_crc = p.len >= 2 ? crc16(p.data, p.len - 2) : 0;
+    p.calculated_crc = p.len < 2 ? 0 : crc >= 0 ? crc : crc16(p.data, p.len - 2);
     p.valid_crc = p.len >= 2 && p.carried_crc == p.calculated_crc;
     p.valid_header = valid_header(p.data, p.len);
     p.correlated_count = 0;
@@ -77,6 +78,7 @@ struct Queued {
     int64_t addr;
     int corrected;
     size_t off, len;                 // bytes[off .. off + len)
+    int crc;                         // the calculated CRC of all `len` bytes where it came with them, -1: not known
 };
 
 struct Sink {
@@ -84,8 +86,13 @@ struct Sink {
     std::vector<uint8_t> bytes;
     void push(const std::vector<uint8_t> &data, int64_t addr, int corrected, int /*source*/)
     {
-        q.push_back(Queued{addr, corrected, bytes.size(), data.size()});
+        q.push_back(Queued{addr, corrected, bytes.size(), data.size(), -1});
         bytes.insert(bytes.end(), data.begin(), data.end());
+    }
+    void push_framed(const uint8_t *data, size_t len, int64_t addr, int crc)
+    {
+        q.push_back(Queued{addr, 0, bytes.size(), len, crc});
+        bytes.insert(bytes.end(), data, data + len);
     }
     void drop_front(size_t take)
     {
@@ -261,6 +268,8 @@ struct pm_codec {
     virtual ~pm_codec() {}
     // feed_many for a fresh decoder with the stream's pm_stream_scan record and list; false: the list does not fit the stream
     virtual bool feed_scanned(const uint8_t *d, const int64_t *a, int64_t n, const uint8_t *scan) = 0;
+    // the same with the frame table and the frame area of a block made with pm_scan_job.frames (AX.25 only)
+    virtual bool feed_framed(const uint8_t *, const int64_t *, int64_t, const uint8_t *) { return false; }
     virtual void feed(uint8_t byte, int64_t addr, Sink &sink) = 0;
     virtual void feed_many(const uint8_t *d, const int64_t *a, int64_t n)
     {
@@ -495,6 +504,41 @@ struct Ax25 : pm_codec {
             take_from(F, (P >> 3) + 1);
         }
         take_from(last_flag, n);                             // the registers as the call leaves them (after a bail: the rest through the table)
+        return true;
+    }
+
+    // feed_scanned with the frames themselves from the device: every listed flag's frame is queued as the frame area holds it, and only
+    // what lies behind the stream's last flag (or behind the last flag in front of a bail) goes through the registers
+    bool feed_framed(const uint8_t *d, const int64_t *a, int64_t n, const uint8_t *scan) override
+    {
+        if (!skim_on || n < 24) {
+            run(d, a, 0, n);
+            return true;
+        }
+        int64_t last_flag;
+        int32_t events;
+        memcpy(&last_flag, scan + 16, 8);
+        memcpy(&events, scan + 24, 4);
+        if (events < 0 || events > n / 19 + 2 || last_flag < -1 || last_flag > 8 * n) return false;
+        const uint8_t *table = scan + PM_SCAN_HEAD + PM_SCAN_LIST_BYTES(0, n) + (n + 7) / 8 * 8, *area = table + PM_SCAN_FRAME_TABLE_BYTES(n);
+        int64_t cursor = 0;
+        for (int32_t e = 0; e < events; ++e) {
+            uint32_t pf[2], crc;
+            int32_t len;
+            memcpy(pf, scan + PM_SCAN_HEAD + 8 * (size_t)e, 8);
+            memcpy(&len, table + 8 * (size_t)e, 4);
+            memcpy(&crc, table + 8 * (size_t)e + 4, 4);
+            const int64_t P = pf[0], F = pf[1] == 0xFFFFFFFFu ? -1 : (int64_t)pf[1];
+            if ((P >> 3) >= n || F > P || (P >> 3) + 1 < cursor) return false;
+            cursor = (P >> 3) + 1;
+            const int64_t from = F < 0 ? 0 : F, at = from >> 3;
+            if (len < 0 || len > (P - from) / 8 || at + len > n || crc > 0xFFFFu) return false;
+            if (len > 0) sink.push_framed(area + at, (size_t)len, a[P >> 3], (int)crc);
+        }
+        // feed_scanned's last step.  The byte that holds the last flag's closing zero is taken again: with no byte counted the flag closes nothing
+        const int64_t sb = last_flag >= 0 ? (last_flag - 1) >> 3 : 0;
+        if (sb > 0) reposition(d, sb);
+        run(d, a, sb, n);
         return true;
     }
 
@@ -1183,6 +1227,20 @@ int pm_codec_decode_scanned(pm_codec *c, const uint8_t *h_plain, const int64_t *
     return PM_OK;
 }
 
+int pm_codec_decode_framed(pm_codec *c, const uint8_t *h_plain, const int64_t *h_addr, int64_t n, const void *h_scan, int64_t *h_pending)
+{
+    if (!c || n < 0 || (n > 0 && (!h_plain || !h_addr)) || !h_scan || !h_pending)
+        return pm_set_error(PM_ERR_ARG, "pm_codec_decode_framed: bad argument");
+    if (c->kind != 0) return pm_set_error(PM_ERR_ARG, "pm_codec_decode_framed: frames are made for AX.25 codecs only");
+    if (!c->fresh) return pm_set_error(PM_ERR_ARG, "pm_codec_decode_framed: the codec has been fed before (the lists are made for a just-created decoder)");
+    c->fresh = false;
+    c->fed += n;
+    if (!c->feed_framed(h_plain, h_addr, n, static_cast<const uint8_t *>(h_scan)))
+        return pm_set_error(PM_ERR_ARG, "pm_codec_decode_framed: the event list or the frame table does not belong to a stream of %lld bytes", (long long)n);
+    *h_pending = (int64_t)c->sink.q.size();
+    return PM_OK;
+}
+
 int pm_codec_walked(pm_codec *c, int64_t *h_walked, int64_t *h_jumped)
 {
     if (!c) return pm_set_error(PM_ERR_ARG, "pm_codec_walked: no codec");
@@ -1208,14 +1266,14 @@ static int codec_fetch(pm_codec *c, pm_packet *h_out, int64_t cap, int64_t *h_co
         p.source_decoder = c->source;
         memcpy(p.data, bytes, (size_t)p.len);
         if (!clean) memset(p.data + p.len, 0, sizeof(p.data) - (size_t)p.len);
-        finalize(p);
+        finalize(p, src.len > PM_PKT_MAX ? -1 : src.crc);
         if (src.len > PM_PKT_MAX) {
             // A frame longer than a row: the reference's AX.25 decoder never drops collected bytes when its byte counter wraps at 1023
             // (ax25.py:41-47), so a flag after a long stretch without one can close a frame of any length.  The row keeps its first
             // PM_PKT_MAX bytes; CRC and validity are those of the WHOLE frame, as PacketMeta.CalcCRC would find them.
             const size_t L = src.len;
             p.carried_crc = bytes[L - 1] * 256 + bytes[L - 2];
-            p.calculated_crc = crc16(bytes, (int)(L - 2));
+            p.calculated_crc = src.crc >= 0 ? src.crc : crc16(bytes, (int)(L - 2));
             p.valid_crc = p.carried_crc == p.calculated_crc;
         }
     }
@@ -1253,7 +1311,8 @@ int pm_host_decode_batch(pm_host_job *jobs, int njobs, int threads)
             const uint8_t *bytes = scan + PM_SCAN_HEAD + PM_SCAN_LIST_BYTES(q.codec->kind, q.n);
             if (q.h_plain && q.n > 0) memcpy(q.h_plain, bytes, (size_t)q.n);
             memcpy(&q.lfsr_state, scan, 8);
-            q.status = pm_codec_decode_scanned(q.codec, bytes, addr, q.n, scan, &q.pending);
+            q.status = q.scan_frames ? pm_codec_decode_framed(q.codec, bytes, addr, q.n, scan, &q.pending)
+                                     : pm_codec_decode_scanned(q.codec, bytes, addr, q.n, scan, &q.pending);
             return;
         }
         uint8_t *out = q.h_plain ? q.h_plain : plain.data();

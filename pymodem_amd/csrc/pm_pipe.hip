@@ -143,6 +143,7 @@ struct pm_pipe {
     unsigned long long *d_lists = nullptr;               // per block: nsweeps lists of kSweepCap entries (what a matrix-pipe sweep's workgroups did not decide themselves)
     std::vector<int> free_cells;
     bool keep_slices = false, trace = false;
+    bool frames = false;                 // pipe_frames: scan, and the AX.25 chains' scan jobs write their frames (pm_scan_job.frames), which the host stage queues as they are
     bool scan = false;                   // pipe_scan of the context the pipeline was made on: pm_stream_scan behind the slicers, the host stage decodes from its lists
     bool host_copy = false;              // PM_PIPE_HOST_COPY: the slicers' compact output through a device block and a copy (round 4), not written to the host block by the kernel
     bool skip_decode = false;            // PM_PIPE_SKIP_DECODE (diagnosis only): the host stage decodes nothing -- what the GPU stages alone sustain
@@ -450,6 +451,7 @@ void slice_worker(pm_pipe *p, int wi)
             for (size_t k = 0; k < nscan; ++k) {
                 const int64_t cnt = jobs[(size_t)jidx[k]].count;
                 dense_cap += PM_SCAN_HEAD + (size_t)PM_SCAN_LIST_BYTES(p->chains[k % nch].codec_kind, cnt) + ((size_t)cnt + 7) / 8 * 8;
+                if (p->frames && p->chains[k % nch].codec_kind == 0) dense_cap += (size_t)PM_SCAN_FRAME_TABLE_BYTES(cnt) + (size_t)PM_SCAN_FRAME_AREA_BYTES(cnt);
             }
             dense_cap += 256 * ((nscan + 63) / 64);
             // The compact kernel writes the batch's output STRAIGHT into a page-locked host block (the device reaches it over the link:
@@ -501,7 +503,7 @@ void slice_worker(pm_pipe *p, int wi)
                 for (size_t k = 0; k < nscan; ++k) {
                     const pm_pipe_chain &ch = p->chains[k % nch];
                     const pm_slice_job &q = jobs[(size_t)jidx[k]];
-                    sj[k] = pm_scan_job{q.d_data, q.count, ch.lfsr_poly, 0, ch.lfsr_invert, ch.codec_kind, ch.sync_tol, 0};
+                    sj[k] = pm_scan_job{q.d_data, q.count, ch.lfsr_poly, 0, ch.lfsr_invert, ch.codec_kind, ch.sync_tol, p->frames && ch.codec_kind == 0 ? 1 : 0};
                 }
                 for (size_t j0 = 0; j0 < nscan && !rc; j0 += 64) {
                     const int nj = (int)std::min<size_t>(64, nscan - j0);
@@ -607,7 +609,10 @@ void host_worker(pm_pipe *p)
                 j.lfsr_poly = ch.lfsr_poly;
                 j.lfsr_state = 0;
                 j.lfsr_invert = ch.lfsr_invert;
-                if (!r.scan_off.empty() && !p->skip_decode) j.h_scan = r.block->p + r.scan_off[c];
+                if (!r.scan_off.empty() && !p->skip_decode) {
+                    j.h_scan = r.block->p + r.scan_off[c];
+                    j.scan_frames = p->frames && ch.codec_kind == 0;
+                }
             }
             if (!rc && p->keep_slices) {
                 // the slicer's output as it reached the host, addresses in full, and room for the LFSR's bytes (pm_host_job.h_plain)
@@ -747,7 +752,8 @@ int pm_pipe_create(pm_ctx *ctx, const pm_pipe_desc *desc, pm_pipe **out)
     const int nd = d.demod_streams > 0 ? std::min(d.demod_streams, 4) : 2;
     p->slots = std::max(2, p->slots);
     p->keep_slices = d.keep_slices != 0;
-    p->scan = ctx->tune.pipe_scan != 0;
+    p->frames = ctx->tune.pipe_frames != 0;
+    p->scan = ctx->tune.pipe_scan != 0 || p->frames;
     p->trace = getenv("PM_PIPE_TRACE") != nullptr;
     p->skip_decode = getenv("PM_PIPE_SKIP_DECODE") != nullptr;
     p->host_copy = getenv("PM_PIPE_HOST_COPY") != nullptr;
@@ -905,6 +911,7 @@ int pm_pipe_create(pm_ctx *ctx, const pm_pipe_desc *desc, pm_pipe **out)
             if (!(rc = pm_ctx_create_prio(ctx->device, 1, &s))) {
                 p->side.push_back(s);
                 s->tune.bitscan_tile_words = ctx->tune.bitscan_tile_words;
+                s->tune.bitscan_frame_words = ctx->tune.bitscan_frame_words;
                 rc = pm_slicer_tune(s, 16384);
                 // walkers of 32 k samples: the slicers are a third of the GPU's work now, and a walker re-walks its merge length
                 // (10-20 k samples) whatever the chunk -- 1 + m/L lane-steps per sample; longer chunks cost depth, not work
