@@ -12,16 +12,17 @@
 // With pm_scan_job.frames a fourth launch writes, for every listed flag, the frame it closes -- the de-stuffed bytes the decoder would have
 // collected since the flag in front, and their CRC-16 -- a wave per event, from a copy of the list that the emit launch leaves on the device.
 #include "pm_common.h"
+#include "pm_bitscan_events.h"
 #include "pm_bitscan_frames.h"
 #include <algorithm>
 #include <cstring>
 
 namespace {
 
+using namespace pm_events;        // what decides the event list: pm_bitscan_events.h, which also compiles for the host
+
 constexpr int kScanJobs = 64;
 constexpr int kLanes = 256;                 // lanes of a workgroup = most words of a tile
-constexpr int kBailSpan = 8000;             // bits without a reset after which the host's skim gives up (pm_codec.cpp: feed_many)
-constexpr int kCloseBits = 8 * 18 + 7;      // a closing flag's zero is counted bit 8 k + 7, k >= 18 (ax25.py:74-81)
 
 struct ScanJobs {
     const uint8_t *data[kScanJobs];
@@ -36,28 +37,6 @@ struct ScanJobs {
 };
 constexpr int kFrameWaves = 256;            // waves that share a job's events in the frames launch (a wave a workgroup: the others leave at once)
 constexpr uint32_t kClosesNothing = 0xFFFFFFFEu;   // F of the stream's first flag in the device-side copy when no frame ends there
-
-// One tile as the tiles in front of it see it.  Positions are bits from the tile's start, -1: none.  Events at or behind `bail` (the
-// first event of the tile whose span since a reset INSIDE the tile reaches kBailSpan) are left out of last_flag, first_flag and closing.
-struct TileSum {
-    int32_t dropped;                        // stuffed zeros in the tile
-    int32_t first_reset, dropped_to_first;  // the first reset and the stuffed zeros in front of it
-    int32_t last_reset, dropped_after_last;
-    int32_t first_flag, last_flag;
-    int32_t closing;                        // AX.25: closing flags whose reset lies inside the tile; IL2P: candidates
-    int32_t bail;
-    int32_t bits;                           // 1: the first reset is a flag, 2: the first flag is counted in `closing`
-    int32_t pad[2];
-};
-
-// What a tile starts from, left by the combine launch for the emit launch.
-struct TileCarry {
-    int64_t after_reset;                    // first bit after the last reset in front of the tile (0: none yet)
-    int64_t after_flag;                     // first bit after the last flag in front of it, -1: none
-    int64_t bail;                           // the stream's bail bit if it lies in this tile, -1 otherwise
-    int32_t dropped;                        // stuffed zeros between after_reset and the tile
-    int32_t events;                         // events of the tiles in front; -1: the stream has bailed before this tile
-};
 
 __device__ inline uint64_t load_word(const uint8_t *d, int64_t n, int64_t w)
 {
@@ -84,20 +63,6 @@ __device__ inline uint64_t plain_word(const ScanJobs &J, int j, int64_t w, uint6
     return J.invert[j] ? ~o : o;
 }
 
-// segment of consecutive words for the tile's one scan: stuffed zeros, the last reset with the zeros up to it, the last flag
-struct Seg {
-    int32_t s, ev, cs, fl;
-};
-__device__ inline Seg seg_join(const Seg &a, const Seg &b)
-{
-    Seg r;
-    r.s = a.s + b.s;
-    r.ev = b.ev >= 0 ? b.ev : a.ev;
-    r.cs = b.ev >= 0 ? a.s + b.cs : a.cs;
-    r.fl = b.fl >= 0 ? b.fl : a.fl;
-    return r;
-}
-
 template <class T, class Op>
 __device__ inline T block_scan(T v, T *lds, Op op)      // inclusive over the workgroup's lanes; lds[t] holds lane t's result afterwards
 {
@@ -118,72 +83,33 @@ __device__ inline T block_scan(T v, T *lds, Op op)      // inclusive over the wo
     return v;
 }
 
-// the AX.25 patterns of one word (pm_codec.cpp: feed_many): stuffed zeros, resets, flags
-struct Marks {
-    uint64_t S, ev, flag;
-};
-__device__ inline Marks ax25_marks(uint64_t w, uint64_t prev, uint64_t valid)
-{
-    const uint64_t e1 = (w << 1) | (prev >> 63), e2 = (w << 2) | (prev >> 62), e3 = (w << 3) | (prev >> 61), e4 = (w << 4) | (prev >> 60),
-                   e5 = (w << 5) | (prev >> 59), e6 = (w << 6) | (prev >> 58), e7 = (w << 7) | (prev >> 57);
-    const uint64_t o5 = e1 & e2 & e3 & e4 & e5;
-    Marks m;
-    m.S = ~w & o5 & ~e6 & valid;
-    m.ev = ~w & o5 & e6 & valid;
-    m.flag = m.ev & ~e7;
-    return m;
-}
-
-// Lane state for its word's events: where the tile's last reset / flag in front of the word lie (bits from the tile's start; -1: none
-// inside the tile) and the stuffed zeros up to there and up to the word.  fn(P, is_flag, R, dropped, F): the event at bit P; R: first
-// bit after the reset in front of it inside the tile (-1: none, `dropped` then counts from the tile's start); F likewise for flags.
-struct LaneIn {
-    Marks m;
-    int32_t base, R, sR, exS, F;
-};
-template <class Fn>
-__device__ inline void walk_events(const LaneIn &in, Fn fn)
-{
-    int32_t R = in.R, sR = in.sR, F = in.F;
-    for (uint64_t e = in.m.ev; e; e &= e - 1) {
-        const int i = __builtin_ctzll(e);
-        const int32_t P = in.base + i, here = in.exS + __popcll(in.m.S & ((1ull << i) - 1));
-        const bool is_flag = (in.m.flag >> i) & 1;
-        if (!fn(P, is_flag, R, here - sR, F)) return;
-        R = P + 1;
-        sR = here;
-        if (is_flag) F = P + 1;
-    }
-}
-
+// The lanes' segments joined by one scan: every lane's state for its word's events, and the whole tile's segment.
 __device__ inline LaneIn lane_prepare(const Marks &m, bool active, Seg *lds, Seg *total)
 {
-    Seg mine{0, -1, 0, -1};
-    if (active) {
-        mine.s = __popcll(m.S);
-        if (m.ev) {
-            const int hi = 63 - __builtin_clzll(m.ev);
-            mine.ev = (int)threadIdx.x * 64 + hi;
-            mine.cs = __popcll(m.S & ((2ull << hi) - 1));
-        }
-        if (m.flag) mine.fl = (int)threadIdx.x * 64 + 63 - __builtin_clzll(m.flag);
-    }
-    block_scan(mine, lds, [](const Seg &a, const Seg &b) { return seg_join(a, b); });
-    const Seg before = threadIdx.x ? lds[threadIdx.x - 1] : Seg{0, -1, 0, -1};
+    block_scan(lane_seg(m, active, (int)threadIdx.x), lds, [](const Seg &a, const Seg &b) { return seg_join(a, b); });
+    const Seg before = threadIdx.x ? lds[threadIdx.x - 1] : seg_none();
     *total = lds[kLanes - 1];
     __syncthreads();
-    LaneIn in;
-    in.m = m;
-    if (!active) in.m.ev = 0;
-    in.base = (int)threadIdx.x * 64;
-    in.R = before.ev >= 0 ? before.ev + 1 : -1;
-    in.sR = before.ev >= 0 ? before.cs : 0;
-    in.exS = before.s;
-    in.F = before.fl >= 0 ? before.fl + 1 : -1;
-    return in;
+    return lane_in(m, active, (int)threadIdx.x, before);
 }
 
-__device__ inline bool closes(int64_t T) { return (T & 7) == 7 && T >= kCloseBits; }
+// the tile launch's accumulator for pm_events::tile_summarise: the summary in LDS, the lanes' shares through LDS atomics
+struct TileSumLds {
+    TileSum *ts;
+    __device__ void first_reset(int32_t P, int32_t dropped, bool is_flag)
+    {
+        ts->first_reset = P;
+        ts->dropped_to_first = dropped;
+        if (is_flag) atomicOr(&ts->bits, 1);
+    }
+    __device__ void first_flag(int32_t P, bool c)
+    {
+        ts->first_flag = P;
+        if (c) atomicOr(&ts->bits, 2);
+    }
+    __device__ void closing(int count) { atomicAdd(&ts->closing, count); }
+    __device__ void last_flag(int32_t P) { atomicMax(&ts->last_flag, P); }
+};
 
 __device__ inline int job_of_tile(const ScanJobs &J, int tile)
 {
@@ -209,15 +135,14 @@ __global__ __launch_bounds__(kLanes) void bitscan_tile_kernel(ScanJobs J, uint8_
     uint64_t x = 0, xp = 0, valid = 0;
     if (active) {
         const uint64_t i0 = load_word(d, n, w), i1 = load_word(d, n, w - 1), i2 = load_word(d, n, w - 2);
-        const int64_t have = n - 8 * w;
-        valid = have >= 8 ? ~0ull : (1ull << (8 * have)) - 1;
+        valid = valid_bits(n, w);
         x = plain_word(J, j, w, i0, i1) & valid;
         xp = w ? plain_word(J, j, w - 1, i1, i2) : 0;           // (a fresh decoder: zeros in front of the stream)
         *reinterpret_cast<uint64_t *>(plain + 8 * w) = __builtin_bswap64(__brevll(x));       // the bytes are padded to 8: the last store is whole
     }
     if (threadIdx.x == 0) {
-        ts = TileSum{0, -1, 0, -1, 0, -1, -1, 0, -1, 0, {0, 0}};
-        ts.bail = 0x7FFFFFFF;
+        ts = tile_sum_empty();
+        ts.bail = kNoBail;
     }
     __syncthreads();
     if (kind == 1) {
@@ -234,7 +159,8 @@ __global__ __launch_bounds__(kLanes) void bitscan_tile_kernel(ScanJobs J, uint8_
                 bool hit = false;
                 for (int s = 0; s < 8; ++s) {
                     const uint32_t v = (uint32_t)(win >> (7 - s));
-                    hit = hit || __popc((v & 0xFFFFFFu) ^ 0xF15E48u) <= tol || __popc(v ^ 0x5D57DF7Fu) <= tol;
+                    // (__popc is unsigned: compared as such, a tol of -1 would let every byte through)
+                    hit = hit || (int)__popc((v & 0xFFFFFFu) ^ 0xF15E48u) <= tol || (int)__popc(v ^ 0x5D57DF7Fu) <= tol;
                 }
                 bits |= (unsigned)hit << b;
             }
@@ -246,47 +172,16 @@ __global__ __launch_bounds__(kLanes) void bitscan_tile_kernel(ScanJobs J, uint8_
     } else if (kind == 0) {
         Seg total;
         const LaneIn in = lane_prepare(ax25_marks(x, xp, valid), active, lds, &total);
-        int cand = 0x7FFFFFFF;
-        walk_events(in, [&](int32_t P, bool, int32_t R, int32_t, int32_t) {
-            if (R >= 0 && P - R >= kBailSpan) {
-                cand = P;
-                return false;
-            }
-            return true;
-        });
-        if (cand != 0x7FFFFFFF) atomicMin(&ts.bail, cand);
+        const int32_t cand = tile_bail_candidate(in);
+        if (cand != kNoBail) atomicMin(&ts.bail, cand);
         __syncthreads();
-        const int limit = ts.bail;
-        int closing = 0, last_flag = -1;
-        walk_events(in, [&](int32_t P, bool is_flag, int32_t R, int32_t dropped, int32_t F) {
-            if (P >= limit) return false;
-            if (R < 0) {                                        // the tile's first reset: one lane meets it
-                ts.first_reset = P;
-                ts.dropped_to_first = dropped;
-                if (is_flag) atomicOr(&ts.bits, 1);
-            }
-            if (is_flag) {
-                const bool c = R >= 0 && closes((int64_t)(P - R) - dropped);
-                if (F < 0) {                                    // the tile's first flag
-                    ts.first_flag = P;
-                    if (c) atomicOr(&ts.bits, 2);
-                }
-                closing += c;
-                last_flag = P;
-            }
-            return true;
-        });
-        if (closing) atomicAdd(&ts.closing, closing);
-        if (last_flag >= 0) atomicMax(&ts.last_flag, last_flag);
-        if (threadIdx.x == 0) {
-            ts.dropped = total.s;
-            ts.last_reset = total.ev;
-            ts.dropped_after_last = total.ev >= 0 ? total.s - total.cs : total.s;
-        }
+        TileSumLds acc{&ts};
+        tile_summarise(in, ts.bail, acc);
+        if (threadIdx.x == 0) tile_totals(ts, total);
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        if (ts.bail == 0x7FFFFFFF) ts.bail = -1;
+        if (ts.bail == kNoBail) ts.bail = -1;
         sums[tile] = ts;
     }
 }
@@ -297,43 +192,17 @@ __global__ __launch_bounds__(64) void bitscan_combine_kernel(ScanJobs J, uint8_t
     const int j = blockIdx.x, lane = threadIdx.x, tw = J.tile_words;
     const int t0 = J.tile0[j], nt = J.tile0[j + 1] - t0;
     const int kind = J.kind[j];
-    int64_t R = 0, LF = -1, bail = -1;
-    int32_t since = 0, events = 0, cands = 0;
+    Combine st = combine_start();
+    int32_t cands = 0;
     for (int r0 = 0; r0 < nt; r0 += 64) {
-        TileSum s = TileSum{0, -1, 0, -1, 0, -1, -1, 0, -1, 0, {0, 0}};
+        TileSum s = tile_sum_empty();
         if (r0 + lane < nt) s = sums[t0 + r0 + lane];
         TileCarry mine{0, -1, -1, 0, -1};
         for (int l = 0; l < 64 && r0 + l < nt; ++l) {
-            const int32_t dropped = __shfl(s.dropped, l), first_reset = __shfl(s.first_reset, l), dropped_to_first = __shfl(s.dropped_to_first, l),
-                          last_reset = __shfl(s.last_reset, l), dropped_after_last = __shfl(s.dropped_after_last, l), first_flag = __shfl(s.first_flag, l),
-                          last_flag = __shfl(s.last_flag, l), closing = __shfl(s.closing, l), tbail = __shfl(s.bail, l), bits = __shfl(s.bits, l);
-            const int64_t B = (int64_t)(r0 + l) * tw * 64;
-            TileCarry c{R, LF, -1, since, bail >= 0 ? -1 : events};
-            cands += closing;
-            if (kind == 0 && bail < 0) {
-                if (first_reset >= 0) {
-                    const int64_t P0 = B + first_reset, span = P0 - R;
-                    if (span >= kBailSpan) {
-                        bail = c.bail = P0;
-                    } else {
-                        if (bits & 1) {
-                            if (LF < 0 || closes(span - (since + dropped_to_first))) ++events;
-                        } else if (LF < 0 && first_flag >= 0 && !(bits & 2)) {
-                            ++events;                           // the stream's first flag, whatever it closes
-                        }
-                        events += closing;
-                        if (last_flag >= 0) LF = B + last_flag + 1;
-                        if (tbail >= 0) {
-                            bail = c.bail = B + tbail;
-                        } else {
-                            R = B + last_reset + 1;
-                            since = dropped_after_last;
-                        }
-                    }
-                } else {
-                    since += dropped;
-                }
-            }
+            const TileSum of{__shfl(s.dropped, l), __shfl(s.first_reset, l), __shfl(s.dropped_to_first, l), __shfl(s.last_reset, l), __shfl(s.dropped_after_last, l),
+                             __shfl(s.first_flag, l), __shfl(s.last_flag, l), __shfl(s.closing, l), __shfl(s.bail, l), __shfl(s.bits, l), {0, 0}};
+            cands += of.closing;
+            const TileCarry c = kind == 0 ? combine_step(st, of, (int64_t)(r0 + l) * tw * 64) : combine_carry(st);
             if (l == lane) mine = c;
         }
         if (r0 + lane < nt) carries[t0 + r0 + lane] = mine;
@@ -346,11 +215,12 @@ __global__ __launch_bounds__(64) void bitscan_combine_kernel(ScanJobs J, uint8_t
             if ((J.data[j][t >> 3] >> (7 - (t & 7))) & 1) reg ^= J.poly[j] >> (T - t);
         uint8_t *rec = block + J.off[j];
         *reinterpret_cast<uint64_t *>(rec) = reg;
-        *reinterpret_cast<int64_t *>(rec + 8) = bail;
-        *reinterpret_cast<int64_t *>(rec + 16) = kind == 0 ? LF : -1;
-        *reinterpret_cast<int32_t *>(rec + 24) = kind == 0 ? events : 0;
+        const Record r = combine_record(st);
+        *reinterpret_cast<int64_t *>(rec + 8) = r.bail_bit;
+        *reinterpret_cast<int64_t *>(rec + 16) = kind == 0 ? r.last_flag : -1;
+        *reinterpret_cast<int32_t *>(rec + 24) = kind == 0 ? r.events : 0;
         *reinterpret_cast<int32_t *>(rec + 28) = kind == 1 ? cands : 0;
-        if (counts) counts[j] = kind == 0 ? events : 0;      // for the frames launch: the block may be host memory, nothing is read back from it
+        if (counts) counts[j] = kind == 0 ? r.events : 0;      // for the frames launch: the block may be host memory, nothing is read back from it
     }
 }
 
@@ -370,37 +240,24 @@ __global__ __launch_bounds__(kLanes) void bitscan_emit_kernel(ScanJobs J, uint8_
     if (active) {
         const uint8_t *d = J.data[j];
         const uint64_t i0 = load_word(d, n, w), i1 = load_word(d, n, w - 1), i2 = load_word(d, n, w - 2);
-        const int64_t have = n - 8 * w;
-        valid = have >= 8 ? ~0ull : (1ull << (8 * have)) - 1;
+        valid = valid_bits(n, w);
         x = plain_word(J, j, w, i0, i1) & valid;
         xp = w ? plain_word(J, j, w - 1, i1, i2) : 0;
     }
     Seg total;
     const LaneIn in = lane_prepare(ax25_marks(x, xp, valid), active, lds, &total);
-    const int64_t limit = c.bail >= 0 ? c.bail : INT64_MAX;
-    // a closing flag has 151 counted bits behind it: a word holds one at most, and the stream's first flag beside it
-    uint2 found[2];
-    int nfound = 0, nothing = 0;                            // nothing: bit k set when found[k] closes no frame (the stream's first flag only)
-    walk_events(in, [&](int32_t P, bool is_flag, int32_t R, int32_t dropped, int32_t F) {
-        const int64_t Pa = B + P;
-        if (Pa >= limit) return false;
-        if (!is_flag) return true;
-        const int64_t T = R >= 0 ? (int64_t)(P - R) - dropped : (Pa - c.after_reset) - ((int64_t)c.dropped + dropped);
-        const int64_t Fa = F >= 0 ? B + F : c.after_flag;
-        if ((Fa < 0 || closes(T)) && nfound < 2) {
-            if (!closes(T)) nothing |= 1 << nfound;
-            found[nfound++] = make_uint2((uint32_t)Pa, (uint32_t)Fa);
-        }
-        return true;
-    });
+    // two places: a word holds one closing flag at most, and the stream's first flag beside it (pm_events::Listed; held by
+    // tests/test_bitscan_core.py, where no lane of any stream at any tile size wants a third)
+    const Listed l = emit_lane(in, c, B);
+    const int nfound = listed_count(l);
     block_scan((int32_t)nfound, cnt, [](int32_t a, int32_t b) { return a + b; });
     const int64_t at = (int64_t)c.events + (threadIdx.x ? cnt[threadIdx.x - 1] : 0), cap = n / 19 + 2;
     uint2 *events = reinterpret_cast<uint2 *>(block + J.off[j] + PM_SCAN_HEAD);
     for (int k = 0; k < nfound; ++k)
-        if (at + k < cap) events[at + k] = found[k];
+        if (at + k < cap) events[at + k] = make_uint2(listed_P(l, k), listed_F(l, k));
     if (J.ev0[j] >= 0)
         for (int k = 0; k < nfound; ++k)
-            if (at + k < cap) copies[J.ev0[j] + at + k] = make_uint2(found[k].x, (nothing >> k) & 1 ? kClosesNothing : found[k].y);
+            if (at + k < cap) copies[J.ev0[j] + at + k] = make_uint2(listed_P(l, k), (l.nothing >> k) & 1 ? kClosesNothing : listed_F(l, k));
 }
 
 // Launch 4 (pm_scan_job.frames): a wave per listed flag {P, F} -- the events e, e + waves, ... of its job, the count read from the combine

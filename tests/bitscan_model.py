@@ -38,6 +38,11 @@ def ax25_model(plain):
     return events, bail, last_flag
 
 
+@functools.lru_cache(maxsize=None)
+def _pop16():
+    return np.array([bin(v).count("1") for v in range(65536)], dtype=np.int64)
+
+
 def il2p_model(plain, tol):
     """One flag per byte k: some bit offset S of byte k has, in the 32 bits that end there, 24 bits within tol of the sync word or
     32 bits within tol of 0x5D57DF7F (il2p.py:367-376).  Bytes 0..3 have no flag."""
@@ -47,7 +52,7 @@ def il2p_model(plain, tol):
     if n < 5:
         return hit
     win = (d[0:n - 4] << np.uint64(32)) | (d[1:n - 3] << np.uint64(24)) | (d[2:n - 2] << np.uint64(16)) | (d[3:n - 1] << np.uint64(8)) | d[4:n]
-    pop = np.array([bin(v).count("1") for v in range(65536)], dtype=np.int64)
+    pop = _pop16()
 
     def popcount32(v):
         return pop[(v & np.uint64(0xFFFF)).astype(np.int64)] + pop[((v >> np.uint64(16)) & np.uint64(0xFFFF)).astype(np.int64)]
@@ -136,7 +141,113 @@ def ax25_streams():
     short = _pack([1, 1, 0] + FLAG * 2 + siggen.ax25_hdlc_bits(_frame(19, 3), pre_flags=1))
     for n in (0, 1, 23, 24, 25):
         out[f"short{n}"] = short[:n].copy()
+    out.update(edge_streams())
     return out
+
+
+# ---- streams for what the tiles, the bail and the stream's end decide -------------------------------------------------------------
+CALM = np.array([0x55, 0xAA, 0x33, 0x66, 0x5A, 0x24], dtype=np.uint8)      # no run of four ones in any sequence of them
+TILE_BITS = 8 * 2048                                                        # the default tile: 256 words
+SPANS = (7999, 8000, 8001)                                                  # raw bits from a reset to the next flag's zero: the bail is at 8000
+STRADDLE_OFFSETS = (-16, -8) + tuple(range(-7, 8)) + (8, 16)                # bits from a multiple of TILE_BITS
+
+
+def _calm_bits(seed, nbits):
+    """nbits bits that hold no run of four ones, the last one a zero"""
+    bits = np.unpackbits(np.random.default_rng(seed).choice(CALM, nbits // 8 + 1)).tolist()[:nbits]
+    if bits:
+        bits[-1] = 0
+    return bits
+
+
+def _span_bits(S, stuffed, seed):
+    """S bits without a reset that end in six ones: behind a reset and in front of a zero, that zero is a flag's, S raw bits behind
+    the reset.  stuffed: 21 zeros behind five ones among them, so that the counted bits are 21 fewer than the raw ones."""
+    fill = []
+    if stuffed:
+        for k in range(21):
+            fill += _calm_bits(seed + k, 80) + [0, 1, 1, 1, 1, 1, 0]
+    fill += _calm_bits(seed + 99, S - 6 - len(fill))
+    return fill + [1] * 6
+
+
+def _first_stuffed(bits):
+    """index of the first zero behind five ones"""
+    ones = 0
+    for k, b in enumerate(bits):
+        if not b and ones == 5:
+            return k
+        ones = ones + 1 if b else 0
+    raise AssertionError("no stuffed zero")
+
+
+def _straddle(piece, at, seed):
+    """`piece` once per offset d of STRADDLE_OFFSETS, its bit `at` at bit k TILE_BITS + d of the stream for the k-th of them, random bits
+    (a flag every 128 bits or so: no bail) in between"""
+    rng = np.random.default_rng(seed)
+    bits = []
+    for k, d in enumerate(STRADDLE_OFFSETS):
+        start = (k + 1) * TILE_BITS + d - at
+        bits += _rand_bits(rng, start - 1 - len(bits)) + [0] + piece
+    return bits + _rand_bits(rng, 2400)
+
+
+def straddle_marks():
+    """the bits of a straddle_* stream at which its piece.s marked bit lies, one per offset"""
+    return [(k + 1) * TILE_BITS + d for k, d in enumerate(STRADDLE_OFFSETS)]
+
+
+@functools.lru_cache(maxsize=None)
+def edge_streams():
+    """name -> descrambled bytes"""
+    out = {}
+    body = siggen.ax25_hdlc_bits(_frame(30, 5), pre_flags=0, post_flags=0)
+    # the bail's boundary: a span of S raw bits from the stream's start or from a flag, calm or with stuffed zeros in it, and a whole
+    # frame behind the flag that ends it -- listed for 7999, behind the bail for 8000 and 8001
+    for S in SPANS:
+        for start, lead in (("start", []), ("flag", [1, 0, 1] + FLAG * 2)):
+            for kind in ("calm", "stuffed"):
+                bits = lead + _span_bits(S, kind == "stuffed", 600 + S) + [0] + siggen.ax25_hdlc_bits(_frame(20, S & 15), pre_flags=1, post_flags=2)
+                out[f"span{S}_{start}_{kind}"] = _pack(bits + _rand_bits(np.random.default_rng(S), 64))
+    # a bail late in a long stream: frames, a span from 8 bytes short of the second default tile to 14 bytes into the third, frames
+    rng = np.random.default_rng(41)
+    bits = _rand_bits(rng, 500) + [0] + siggen.ax25_hdlc_bits(_frame(40, 6), pre_flags=2, post_flags=1) + _rand_bits(rng, 3000) + [0]
+    bits += siggen.ax25_hdlc_bits(_frame(25, 7), pre_flags=1, post_flags=1)
+    bits += _rand_bits(rng, TILE_BITS - 64 - 9 - len(bits)) + [0] + FLAG + _calm_bits(42, TILE_BITS + 8 * 14 + 64 - 8) + [1] * 6 + [0]
+    bits += siggen.ax25_hdlc_bits(_frame(33, 2), pre_flags=1, post_flags=2) + _rand_bits(rng, 9000) + [0] + siggen.ax25_hdlc_bits(_frame(22, 3), pre_flags=2)
+    out["late_bail"] = _pack(bits + _rand_bits(rng, 3 * TILE_BITS + 2000 - len(bits)))
+    # what lies across the default tiles' boundaries, at every bit offset and a few whole bytes to either side of each
+    shared = ([0] + [1] * 6) * 9 + [0]
+    out["straddle_flag"] = _pack(_straddle(shared + body + shared + body + FLAG, len(shared) + len(body) + 7, 50))      # the zero of the flag that closes the first frame
+    stuffy = siggen.ax25_hdlc_bits(siggen.ax25_ui_frame("CQ", "N0CAL", [0x7F, 0xFF, 0x41, 0xFF, 0x1F] + list(range(48, 60))), pre_flags=1, post_flags=1)
+    out["straddle_stuffed"] = _pack(_straddle(stuffy, 8 + _first_stuffed(stuffy[8:-8]), 51))                            # the frame's first stuffed zero
+    abort = FLAG + body[:len(body) // 2] + [0] + [1] * 7 + [0]
+    out["straddle_run7"] = _pack(_straddle(abort + FLAG + body + FLAG, len(abort) - 1, 52))                              # the zero behind seven ones
+    f18 = siggen.ax25_hdlc_bits(_frame(18, 4), pre_flags=1, post_flags=1)
+    piece = f18 + _rand_bits(np.random.default_rng(53), 80) + [0] + siggen.ax25_hdlc_bits(_frame(17, 4), pre_flags=3, post_flags=1)
+    out["straddle_bit151"] = _pack(_straddle(piece, len(f18) - 2, 54))           # the 151st counted bit of the 18-byte frame: its flag's last one
+    # many frames back to back, one flag between some and two between others: more events than the frames launch has waves, twice over
+    bits = list(FLAG)
+    for k in range(640):
+        bits += siggen.ax25_hdlc_bits(_frame(19 + k % 7, 1000 + k), pre_flags=0, post_flags=1) + (FLAG if k % 3 == 0 else [])
+    out["many_frames"] = _pack(bits + [0] * 5)
+    # the stream's end inside a word, at every length mod 8: the padding's first bit would complete a flag, a stuffed zero, a run's end
+    for r in range(8):
+        n = 8 * 4 + r + 1
+        head = FLAG + siggen.ax25_hdlc_bits(_frame(19, 30 + r), pre_flags=0, post_flags=1)
+        for name, ones in (("five", 5), ("six", 6), ("seven", 7)):
+            tail = [0] + [1] * ones
+            out[f"end{r}_{name}"] = _pack(head + _calm_bits(700 + r, 8 * n - len(head) - len(tail)) + tail)
+            assert len(out[f"end{r}_{name}"]) == n
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def ax25_block(name):
+    """model_block of the AX.25 stream `name`, made once and shared: read-only"""
+    block = model_block(ax25_streams()[name], 0)
+    block.flags.writeable = False
+    return block
 
 
 def _il2p_bits(seed, flips=0, rng=None):

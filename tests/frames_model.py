@@ -8,7 +8,7 @@ import bitscan_model as M
 from pymodem_amd import siggen
 from pymodem_amd._native import lib, scan_frame_area_bytes, scan_frame_table_bytes
 
-CALM = np.array([0x55, 0xAA, 0x33, 0x66, 0x5A, 0x24], dtype=np.uint8)      # no run of six ones, no five ones before a zero
+CALM = M.CALM                                               # no run of six ones, no five ones before a zero
 
 
 def frame_model(bits, P, F):
@@ -103,6 +103,9 @@ def frame_streams():
     out["long_no_bail"] = M._pack(M.FLAG + _calm(520, 900) + [1] * 8 + [0] + _calm(521, 900) + [1] * 7 + [0] + body + M.FLAG + M._rand_bits(np.random.default_rng(522), 100))
     out["first_closes"] = M._pack(body + M.FLAG + M._rand_bits(np.random.default_rng(523), 200))
     out["first_closes_after_run"] = M._pack([1] * 9 + [0] + body + M.FLAG + M._rand_bits(np.random.default_rng(524), 200))
+    # the same with a second flag behind the first, both in one 64-bit word: the stream's first flag closes the frame begun at the run's end
+    pad = next(p for p in range(64) if (p + 10 + len(body)) % 64 <= 48)
+    out["two_flags_one_word"] = M._pack([1] * (9 + pad) + [0] + body + M.FLAG * 2 + M._rand_bits(np.random.default_rng(525), 200))
     return out
 
 

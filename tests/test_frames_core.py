@@ -39,4 +39,4 @@ def test_every_frame_is_the_model_s(checker, words):
     exe, path, events = checker
     run = subprocess.run([exe, path, str(words)], capture_output=True, text=True)
     assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-2000:]
-    assert run.stdout.strip().endswith(f"{events} events, 0 bad") and events >= 250
+    assert run.stdout.strip().endswith(f"{events} events, 0 bad") and events >= 1258

@@ -1,8 +1,10 @@
 """pm_stream_scan (csrc/pm_bitscan.hip): the LFSR's bytes and register against pm_lfsr_unscramble, the AX.25 event lists and IL2P
 candidate bitmaps against the bit-serial model of bitscan_model.py -- at the smallest tile, where every flag, run of ones, stuffed zero
-and sync word straddles a tile boundary at some bit offset, and at the default -- and the executor with the stage on against the
-executor with it off and against the oracle."""
+and sync word straddles a tile boundary at some bit offset and only the combine's carry decides, at the default, where the scan over the
+lanes decides, and at the sizes in between, where both do (125 and 126 words: the largest tile that cannot bail inside itself and the
+smallest that can) -- and the executor with the stage on against the executor with it off and against the oracle."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
@@ -103,8 +105,8 @@ def _scrambled(plain, small_poly=0x21001):
     return np.packbits(np.array(bits, dtype=np.uint8)) if len(bits) else np.zeros(0, np.uint8), small_poly, 0, 1
 
 
-def _compare(name, part, kind, tol, plain):
-    want = M.split_block(M.model_block(plain, kind, tol), kind, len(plain))
+def _compare(name, part, kind, tol, plain, want_block=None):
+    want = M.split_block(M.model_block(plain, kind, tol) if want_block is None else want_block, kind, len(plain))
     got = M.split_block(part, kind, len(plain))
     for field in ("bail_bit", "last_flag", "events", "candidates"):
         assert got[0][field] == want[0][field], (name, field, int(got[0][field]), int(want[0][field]))
@@ -112,14 +114,62 @@ def _compare(name, part, kind, tol, plain):
     assert np.array_equal(got[2], want[2]), (name, "bytes")
 
 
-@pytest.mark.parametrize("tile", [1, 0])
+@functools.lru_cache(maxsize=None)
+def _ax25_jobs():
+    """every AX.25 stream as a job, scrambled once"""
+    streams = M.ax25_streams()
+    return [_scrambled(streams[k]) + (0, 0) for k in sorted(streams)]
+
+
+@pytest.mark.parametrize("tile", [1, 2, 3, 17, 64, 125, 126, 255, 0])
 def test_ax25_events_equal_the_model(tile):
     ctx = _ctx()
     streams = M.ax25_streams()
     names = sorted(streams)
-    jobs = [_scrambled(streams[k]) + (0, 0) for k in names]
-    for name, part in zip(names, run_scan(ctx, jobs, tile)):
-        _compare(name, part, 0, 0, streams[name])
+    for name, part in zip(names, run_scan(ctx, _ax25_jobs(), tile)):
+        _compare(name, part, 0, 0, streams[name], M.ax25_block(name))
+
+
+NOISE = (1, 7, 8, 9)            # bytes in front of a stream that leave their mark in the register: less than a word, a word, more
+
+
+@functools.lru_cache(maxsize=None)
+def _seeded():
+    """[(name, plain B, B's slicer bytes, register behind A)]: every structured stream B behind 1, 7, 8 and 9 bytes of noise A, A + B
+    scrambled through G3RUH's polynomial, the register behind A from the host's descrambler"""
+    out = []
+    streams = M.ax25_streams()
+    for k, name in enumerate(sorted(streams)):
+        if name.startswith("random") or name == "dense":
+            continue
+        for a in NOISE:
+            noise = np.random.default_rng(1000 * a + k).integers(0, 256, a, dtype=np.uint8)
+            both = np.concatenate([noise, streams[name]])
+            raw = np.packbits(np.array(M.siggen.lfsr_scramble(np.unpackbits(both).tolist(), 0x21001, True), dtype=np.uint8))
+            plain_a, reg = host_lfsr(raw[:a], 0x21001, 0, True)
+            assert np.array_equal(plain_a, noise) and reg != 0
+            out.append((f"{name} behind {a}", streams[name], raw[a:].copy(), reg))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _seeded_block(k, kind):
+    """the model's block for _seeded()[k], made once for both tile sizes: read-only"""
+    block = M.model_block(_seeded()[k][1], kind, 2)
+    block.flags.writeable = False
+    return block
+
+
+@pytest.mark.parametrize("tile", [1, 0])
+@pytest.mark.parametrize("kind", [0, 1])
+def test_a_register_that_is_not_zero_reaches_the_marks(kind, tile):
+    """The incoming register meets word 0 as the lane's own word and as the word in front of lane 1's."""
+    ctx = _ctx()
+    cases = _seeded()
+    jobs = [(raw, 0x21001, reg, 1, kind, 2) for _, _, raw, reg in cases]
+    for k, ((name, plain, raw, reg), part) in enumerate(zip(cases, run_scan(ctx, jobs, tile))):
+        _compare(name, part, kind, 2, plain, _seeded_block(k, kind))
+        assert int(M.split_block(part, kind, len(plain))[0]["lfsr_state"]) == host_lfsr(raw, 0x21001, reg, True)[1], name
 
 
 @pytest.mark.parametrize("tile", [1, 0])
@@ -130,6 +180,21 @@ def test_il2p_candidates_equal_the_model(tile):
     jobs = [_scrambled(streams[k][0], 0x3) + (1, streams[k][1]) for k in names]
     for name, part in zip(names, run_scan(ctx, jobs, tile)):
         _compare(name, part, 1, streams[name][1], streams[name][0])
+
+
+@pytest.mark.parametrize("tol", [-1, 24, 33, 100])
+def test_il2p_sync_tol_at_its_clamps(tol):
+    """pm_stream_scan takes sync_tol into [-1, 33]: below 0 nothing is a candidate, from 24 on every byte behind the fourth is (24 bits
+    differ from the sync word in 24 places at most)."""
+    ctx = _ctx()
+    clamped = max(-1, min(33, tol))
+    streams = M.il2p_streams()
+    names = ["random", "short5"]
+    jobs = [_scrambled(streams[k][0], 0x3) + (1, tol) for k in names]
+    for name, part in zip(names, run_scan(ctx, jobs)):
+        plain = streams[name][0]
+        _compare(name, part, 1, clamped, plain)
+        assert int(M.split_block(part, 1, len(plain))[0]["candidates"]) == (0 if tol < 0 else max(0, len(plain) - 4)), name
 
 
 def test_a_batch_of_forty_streams_and_a_block_too_small():

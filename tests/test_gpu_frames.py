@@ -1,7 +1,9 @@
 """pm_stream_scan with pm_scan_job.frames (csrc/pm_bitscan.hip: bitscan_frames_kernel): the frame table and the frame area against the
 bit-serial model of frames_model.py -- with one word of a frame's span per trip, where every byte boundary, stuffed zero, run end and flag
-straddles a trip, with three, and with the default -- and the executor with frames on against the executor without the scan stage and
-against the oracle."""
+straddles a trip, with three, and with the default, from lists made at the tile sizes of test_gpu_bitscan.py -- and the executor with
+frames on against the executor without the scan stage and against the oracle."""
+import functools
+
 import ctypes
 
 import numpy as np
@@ -30,7 +32,9 @@ def _need(job):
 def run_scan(ctx, jobs, tile=0, words=0, short_by=0):
     """jobs: [(slicer bytes, poly, register, invert, kind, tol, frames)] -> each job's part of the block (or (status, used, need) with
     short_by).  The block starts out as 0xA5 bytes: what the launches do not write shows."""
-    assert len(jobs) <= 64
+    if len(jobs) > 64:                                        # a batch holds 64 jobs
+        assert not short_by
+        return run_scan(ctx, jobs[:64], tile, words) + run_scan(ctx, jobs[64:], tile, words)
     bufs = [ctx.upload(j[0] if len(j[0]) else np.zeros(8, np.uint8)) for j in jobs]
     arr = (ScanJob * len(jobs))()
     for q, b, j in zip(arr, bufs, jobs):
@@ -85,13 +89,21 @@ def _compare_frames(name, part, plain, model):
     assert (part[at + 8 * len(got_table):at + scan_frame_table_bytes(n)] == 0xA5).all(), (name, "places past `events` are not written")
 
 
-@pytest.mark.parametrize("words", [1, 3, 0])
-@pytest.mark.parametrize("tile", [1, 0])
+@functools.lru_cache(maxsize=None)
+def _jobs():
+    """every stream as a job with frames, scrambled once"""
+    streams = FM.all_streams()
+    return [_scrambled(streams[k]) + (0, 0, 1) for k in sorted(streams)]
+
+
+# the frames launch does not read tiles, only the list it is given depends on them: every trip length at the smallest tile and at the
+# default, the default trip at the tile sizes in between
+@pytest.mark.parametrize("tile,words", [(t, w) for t in (1, 0) for w in (1, 3, 0)] + [(t, 0) for t in (2, 3, 17, 64, 125, 126, 255)])
 def test_frames_equal_the_model(models, tile, words):
     ctx = _ctx()
     streams = FM.all_streams()
     names = sorted(streams)
-    jobs = [_scrambled(streams[k]) + (0, 0, 1) for k in names]
+    jobs = _jobs()
     with_frames = run_scan(ctx, jobs, tile, words)
     without = run_scan(ctx, [j[:6] + (0,) for j in jobs], tile, words)
     frames = 0
@@ -99,7 +111,7 @@ def test_frames_equal_the_model(models, tile, words):
         _compare_frames(name, part, streams[name], models[name])
         assert np.array_equal(part[:len(bare)], bare), (name, "what exists without frames is the same with them")
         frames += int((FM.split_frames(part, len(streams[name]))[0]["len"] > 0).sum())
-    assert frames >= 230
+    assert frames >= 1193
 
 
 def test_a_mixed_batch_of_forty_streams_and_a_block_too_small():
