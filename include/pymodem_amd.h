@@ -116,7 +116,7 @@ int pm_fir_valid_i16(pm_ctx *ctx, const int16_t *d_x, int64_t n, const double *d
  * (v_mfma_i32_16x16x64_i8), recombined in binary64.  |d_y[k] - reference sum| <= *h_bound (~1e-9 of sum|taps| * 32768).  m <= 241,
  * d_x 16-byte aligned, h_taps on the HOST; synchronous (plans its tables per call: the pipeline keeps them).  Test and measurement entry. */
 int pm_fir_valid_i16_limbs(pm_ctx *ctx, const int16_t *d_x, int64_t n, const double *h_taps, int m, double *d_y, double *h_bound);
-/* What the certified AFSK sweeps' binary32 roots rely on (csrc/pm_fir.hip: slide_run_f32): the largest error of the device's v_sqrt_f32
+/* What the certified AFSK sweeps' binary32 roots rely on (csrc/pm_afsk.hip: slide_run_f32): the largest error of the device's v_sqrt_f32
  * over ALL 2^24 binary32 values of the binades 2^exponent and 2^(exponent + 1), in units of the result's last place x 1024 (rounded up),
  * against the correctly rounded binary64 root.  Test entry. */
 int pm_ubench_sqrt_f32(pm_ctx *ctx, int exponent, int64_t *h_worst_ulp_1024);
@@ -636,7 +636,7 @@ int64_t pm_correlate_strided(void *h_records, int64_t stride, const int64_t *h_c
  * packets of all of them de-duplicated -- as a pipeline over RECORDINGS that lives entirely inside the library:
  *   pm_pipe_submit   launches the recording's demod stage on one of the demod streams -- for an AFSK group of up to two certified
  *                    sweeps ONE kernel: band-pass, every sweep and the exact chain for whatever it cannot certify, the int16 audio read
- *                    once and one bit per sample and chain written (csrc/pm_fir.hip: afsk_fused8_kernel; other groups: band-pass + a
+ *                    once and one bit per sample and chain written (csrc/pm_afsk.hip: afsk_fused8_kernel; other groups: band-pass + a
  *                    launch per sweep) -- records an event, returns; blocks only while all bitmap slots are in use
  *   slicer threads   (own high-priority streams) wait for the event, take up to `slice_group` consecutive recordings, work off what a
  *                    sweep left on its list (normally nothing; an overflowed list: the exact kernels), run pm_slice_batch +

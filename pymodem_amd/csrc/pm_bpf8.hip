@@ -1,5 +1,5 @@
 // The shared band-pass of an AFSK chain group (afsk.py:151: int16 audio, ~150 real taps) on the int8 matrix pipe, for consumers that
-// need a VALUE WITH A BOUND and not the reference's rounding: the certified gain sweeps (pm_fir.hip).  Every other
+// need a VALUE WITH A BOUND and not the reference's rounding: the certified gain sweeps (pm_afsk.hip).  Every other
 // caller keeps fir_valid_kernel<short>, the reference's sum in its canonical order.
 //
 // Why: in binary64 the band-pass is 148 vector fma per sample, 0.165 ms per recording alone and 29 % of the demod stage's fma issue
@@ -348,7 +348,7 @@ void pm_bpf8_plan_destroy(pm_bpf8_plan *p)
 }
 
 double pm_bpf8_error(const pm_bpf8_plan *p) { return p ? p->err : 0.0; }
-// what a kernel that runs the band-pass as a stage of its own needs (afsk_fused8_kernel, pm_fir.hip): blocks, band table, scales
+// what a kernel that runs the band-pass as a stage of its own needs (afsk_fused8_kernel, pm_afsk.hip): blocks, band table, scales
 int pm_bpf8_plan_view(const pm_bpf8_plan *p, int *kb, const void **d_btab, double *scales6)
 {
     if (!p || p->digits != kMaxDigits || !kb || !d_btab || !scales6) return pm_set_error(PM_ERR_ARG, "pm_bpf8_plan_view: not a four-digit plan");
@@ -400,7 +400,7 @@ int pm_bpf8_rows_max(pm_ctx *ctx, const pm_bpf8_plan *p, const int16_t *const *d
     return PM_OK;
 }
 
-// ---- the low-pass plan of the certified sweeps (kernel: afsk_slide_lpf8_kernel, pm_fir.hip) ---------------------------------------
+// ---- the low-pass plan of the certified sweeps (kernel: afsk_slide_lpf8_kernel, pm_afsk.hip) ---------------------------------------
 int pm_lpf8_plan_create(pm_ctx *ctx, const double *h_taps, int ml, pm_lpf8_plan **out)
 {
     PM_CTX(ctx);

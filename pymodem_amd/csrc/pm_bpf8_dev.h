@@ -1,5 +1,5 @@
 // Device pieces of the int8 band-pass (pm_bpf8.hip has the picture and the error analysis) for kernels that run it as a STAGE of their
-// own -- afsk_fused8_kernel in pm_fir.hip -- with the digit planes at run-time addresses.  The arithmetic is bpf8_kernel's, operation for
+// own -- afsk_fused8_kernel in pm_afsk.hip -- with the digit planes at run-time addresses.  The arithmetic is bpf8_kernel's, operation for
 // operation: a value computed here is the value that kernel writes.
 #pragma once
 #include <hip/hip_runtime.h>

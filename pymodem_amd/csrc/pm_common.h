@@ -143,7 +143,7 @@ int pm_bpf8_run(pm_ctx *ctx, const pm_bpf8_plan *p, const int16_t *d_audio, int6
 // d_keys: rows words of work space; d_redone: null or a counter of the outputs that took the exact chain.  Rows 16-byte aligned.
 int pm_bpf8_rows_max(pm_ctx *ctx, const pm_bpf8_plan *p, const int16_t *const *d_rows, int rows, int64_t n, unsigned long long *d_keys, double *d_out,
                      unsigned long long *d_redone = nullptr);
-// The certified sweeps' low-pass on the same pipe (afsk_slide_lpf8_kernel in pm_fir.hip): taps as three signed base-256 digits
+// The certified sweeps' low-pass on the same pipe (afsk_slide_lpf8_kernel in pm_afsk.hip): taps as three signed base-256 digits
 // q = rint(h 2^S), |q| <= 2^22, the Toeplitz band as MFMA B operands [digit][block][lane] on the device.  ml <= 113.
 struct pm_lpf8_plan {
     int ml = 0, S = 0, device = 0;
@@ -152,7 +152,7 @@ struct pm_lpf8_plan {
     double dlow = 0;                 // bound on the digit product the kernel leaves out: 128 sum|q_0|
     double hmax = 0;
     void *d_btab = nullptr;
-    // made by the fused launch the first time it meets the sweep's templates (pm_fir.hip: afsk_group_run_fused): the four correlator
+    // made by the fused launch the first time it meets the sweep's templates (pm_afsk.hip: afsk_group_run_fused): the four correlator
     // templates reversed and interleaved, for scalar loads; tpl_src / tpl_m say which templates it was made from
     void *d_tpl = nullptr;
     const void *tpl_src[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -203,6 +203,10 @@ int pm_fir8_rows_signs(pm_ctx *ctx, const pm_fir8_plan *p, const double *d_x, in
 // Exactly one of d_y (rows of n - m + 1 doubles, pitch y_stride) and d_bits (sign bitmaps, pitch bits_stride words) is given.
 int pm_fir_rows(pm_ctx *ctx, bool i16, const void *d_x, int64_t x_stride, const void *const *d_x_ptrs, int64_t x_off, bool x_aligned16, int rows,
                 int64_t n, const double *d_taps, int m, double *d_y, int64_t y_stride, uint64_t *d_bits, int64_t bits_stride, int flags);
+// pm_fir_signs_f64_batch (h_x, h_n, h_bits: HOST arrays of `count` streams) with a gate: d_gate == nullptr, or a device word -- the launch
+// (then a small grid that walks the tiles) leaves at once unless *d_gate > gate_above; d_reset: nullptr, or a device word it zeroes either way
+int pm_fir_signs_batch(pm_ctx *ctx, int count, const double *const *h_x, const int64_t *h_n, const double *d_taps, int m, uint64_t *const *h_bits,
+                       int flags, const int *d_gate, int gate_above, int *d_reset);
 // nloops carrier loops resident in device memory; loop l reads input row l / per_row (pm_loops.hip).  modem: PM_MODEM_*.
 int pm_loops_rows(pm_ctx *ctx, int modem, pm_loop *d_loops, int nloops, int per_row, const double *d_table, const int32_t *d_pd,
                   const double *d_x0, const double *d_x1, int64_t x_stride, int64_t n, double *d_o0, double *d_o1, int64_t out_stride);

@@ -2,7 +2,7 @@
 // (psk.py:750-751, 241 taps) -- as CERTIFIED SIGNS on the int8 matrix pipe, for the batch engine (pm_loopbatch.hip).
 //
 // slicer.slice reads `sample >= 0` and nothing else (slicer.py:74-106, :215-231), so what has to be the reference's is the sign of
-// the canonical sum  y[k] = sum_t h[m-1-t] x[k+t]  (one fma per tap, ascending input index, from +0: fir_acc_image in pm_fir.hip),
+// the canonical sum  y[k] = sum_t h[m-1-t] x[k+t]  (one fma per tap, ascending input index, from +0: fir_acc_image in pm_fir_dev.h),
 // not its value.  In binary64 on the vector pipe that sum is 961 fma per sample: 55 GFLOP per ten-minute recording, the first
 // kernel of configs[1] and the second of configs[4] in round 3's profiles.  Here:
 //

@@ -108,7 +108,7 @@ def _sweeps(lines):
 
 
 def _e_combine(lpf, bpf, gains, m):
-    """The 1e-10 term of the sweep's E (pm_fir.hip, sweep_signs / the pipeline's sweeps): every mode's E is at least this."""
+    """The 1e-10 term of the sweep's E (pm_afsk_sweep.h, sweep_bound): every mode's E is at least this."""
     x_bound = float(np.abs(bpf).sum()) * 32768.0
     return 1e-10 * float(np.abs(lpf).sum()) * (1.0 + max(gains)) * float(m) * 1.4143 * x_bound, x_bound
 

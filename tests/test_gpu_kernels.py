@@ -115,7 +115,7 @@ def test_fir_int8_limbs_rejects_what_it_cannot_hold(ctx):
 
 @pytest.mark.parametrize("exponent", [-60, -21, -1, 0, 1, 24, 59, 100])
 def test_v_sqrt_f32_is_within_one_ulp(ctx, exponent):
-    """slide_run_f32 (csrc/pm_fir.hip) takes the roots of the certified sweeps' magnitudes with v_sqrt_f32 and prices the instruction at
+    """slide_run_f32 (csrc/pm_afsk.hip) takes the roots of the certified sweeps' magnitudes with v_sqrt_f32 and prices the instruction at
     one unit in the last place in its bound: here the device evaluates it on every one of the 2^24 binary32 values of two neighbouring
     binades (a root's significand depends on the radicand's significand and its exponent's parity only) against the correctly rounded
     binary64 root."""
