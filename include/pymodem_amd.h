@@ -396,12 +396,39 @@ int pm_slice_compact(pm_ctx *ctx, const pm_slice_job *h_jobs, int njobs, void *d
  *       do not overlap); bytes that no frame covers are not written.
  * One more launch, a wave per event, pm_ctx_tune(ctx, "bitscan_frame_words", 1 .. 64) words of the span per trip (0: 64); results do
  * not depend on it.
+ * With pm_scan_job.packets = 1 (kind 1 only; PM_ERR_ARG otherwise) two more pieces follow the descrambled bytes, for
+ * pm_codec_decode_packets; the pieces in front are byte for byte what they are without it.  An ATTEMPT is what an IL2P decoder with the job's
+ * il2p_crc, il2p_disable_rs and il2p_min_dist does from the bit H at which it enters its header state until it is back in sync search; it
+ * depends on nothing but the descrambled bits from H on.  For a candidate byte k of the bitmap let S be the smallest of its bit offsets
+ * 0 .. 7 at which the sync test hits on the 32 bits that end there: H = 8 k + S + 1.
+ *   the packet table, PM_SCAN_PACKET_TABLE_BYTES(n): {int32 records, int32 placed, 8 bytes zero}, then n / 64 + 2 places of 16 bytes, the first
+ *       `records` of them one per candidate in ascending order (candidates behind the last place get none; places past `records` are not
+ *       written):
+ *           uint32 at       k << 3 | S
+ *           uint32 off      where the packet lies in the area, a multiple of 8 (0xFFFFFFFF: nowhere)
+ *           uint16 count    the header's payload byte count
+ *           uint8  status   0 INCOMPLETE  the stream ends before the attempt's last bit (the header's 120 bits; with a good header its blocks
+ *                                         and, with il2p_crc, the four CRC bytes): nothing but `at` is filled
+ *                           1 HEADER_FAIL the header's RS(2) fails: the attempt ends 120 bits behind H
+ *                           2 DONE        header and every block decode: 13 descrambled header bytes and `count` payload bytes lie at `off`
+ *                           3 BLOCK_FAIL  a block's RS(16) fails: the attempt ends at that block's last bit
+ *                           4 NOT_PLACED  a good, complete header that found no room in the area (this record's and every later one's)
+ *           uint8  corrected  what the attempt adds to the decoder's count of corrected bytes
+ *           uint32 end      the bits from H to where the attempt ends, the CRC bytes not counted
+ *       placed: the records with a place in the area (DONE and BLOCK_FAIL).
+ *   the packet area, PM_SCAN_PACKET_AREA_BYTES(n): records take (13 + count + 7) & ~7 bytes each in ascending order, zeros behind the payload;
+ *       bytes that no DONE record covers are not written.  (A real packet takes more of the stream than of the area, so real packets always
+ *       fit; chance headers and planted overlaps can run the area out.)
+ * Two more launches: one wave per job takes the candidates 64 at a time, a lane a header; pm_ctx_tune(ctx, "bitscan_packet_waves", 1 .. 1024)
+ * waves per job (0: 64) share the placed records' blocks.  Results do not depend on it.
  * *h_used = bytes the batch needs; PM_ERR_CAPACITY (with *h_used set) if block_bytes is less.  n <= 2^29, njobs <= 64.  Tiles of
  * pm_ctx_tune(ctx, "bitscan_tile_words", 1 .. 256) 64-bit words (0: the default, 256); results do not depend on it. */
 #define PM_SCAN_HEAD 32
 #define PM_SCAN_LIST_BYTES(kind, n) ((kind) == 0 ? 8 * ((n) / 19 + 2) : (kind) == 1 ? 8 * (((n) + 63) / 64) : 0)     /* the list's bytes: the descrambled bytes lie behind it */
 #define PM_SCAN_FRAME_TABLE_BYTES(n) (8 * ((n) / 19 + 2))       /* frames: behind the descrambled bytes (padded to 8) ... */
 #define PM_SCAN_FRAME_AREA_BYTES(n) (((n) + 7) / 8 * 8)         /* ... and behind the table */
+#define PM_SCAN_PACKET_TABLE_BYTES(n) (16 + 16 * ((n) / 64 + 2))  /* packets: behind the descrambled bytes (padded to 8) ... */
+#define PM_SCAN_PACKET_AREA_BYTES(n) (((n) + 7) / 8 * 8)          /* ... and behind the table */
 typedef struct pm_scan_job {
     const uint8_t *d_data;
     int64_t n;
@@ -411,6 +438,8 @@ typedef struct pm_scan_job {
     int32_t codec_kind;              /* 0 AX.25, 1 IL2P, -1 none */
     int32_t sync_tol;
     int32_t frames;                  /* 1 (kind 0 only): the frame table and the frame area behind the descrambled bytes */
+    int32_t packets;                 /* 1 (kind 1 only): the packet table and the packet area behind the descrambled bytes ... */
+    int32_t il2p_crc, il2p_disable_rs, il2p_min_dist;      /* ... for a codec with these options (pm_codec_create) */
 } pm_scan_job;
 int pm_stream_scan(pm_ctx *ctx, const pm_scan_job *h_jobs, int njobs, void *d_block, size_t block_bytes, int64_t *h_offsets, size_t *h_used);
 /* How many chunks (= walkers) a batch is cut into on this ctx, within 1024..16384 samples per chunk; 0 restores the default 16384.
@@ -579,6 +608,15 @@ int pm_codec_decode_scanned(pm_codec *c, const uint8_t *h_plain, const int64_t *
  * from there to the end it decodes byte by byte, which leaves the registers as pm_codec_decode would and finds what lies behind a bail.
  * PM_ERR_ARG for a table that cannot belong to the stream (len < 0, more bytes than the span from F to P holds, a frame past byte n). */
 int pm_codec_decode_framed(pm_codec *c, const uint8_t *h_plain, const int64_t *h_addr, int64_t n, const void *h_scan, int64_t *h_pending);
+/* The same for an IL2P codec (created with the job's crc, disable_rs and min_dist) and a block made with pm_scan_job.packets: the decoder
+ * searches as pm_codec_decode_scanned does, and where its own sync test hits at byte k, bit offset S, and the table has a record with
+ * at == k << 3 | S, the record is taken for the attempt -- HEADER_FAIL and BLOCK_FAIL pass over it, DONE queues the packet from the area (the
+ * AX.25 header rebuilt from its 13 bytes; the Hamming-coded CRC from the descrambled bytes behind the last block, or the computed one; the
+ * address that of the byte with the attempt's last bit) -- and the rest of the byte in which it ends goes through the decoder.  Every other
+ * hit (no record, another offset, INCOMPLETE, NOT_PLACED) is decoded bit by bit as ever.  PM_ERR_ARG, with the codec untouched, for a table
+ * that cannot belong to the stream: records above the places or placed above records, `at` not ascending or k outside [4, n), count > 1023,
+ * a placed record outside the area, an attempt that ends behind the stream, a DONE record whose header bytes say another count. */
+int pm_codec_decode_packets(pm_codec *c, const uint8_t *h_plain, const int64_t *h_addr, int64_t n, const void *h_scan, int64_t *h_pending);
 /* Bytes this codec has taken through its byte-by-byte machine so far, and bytes it has passed over (either may be NULL). */
 int pm_codec_walked(pm_codec *c, int64_t *h_walked, int64_t *h_jumped);
 
@@ -605,6 +643,7 @@ typedef struct pm_host_job {
                                   /* h_data, LFSR and codec kind: the descrambled bytes and the register come from there and the */
                                   /* codec goes through pm_codec_decode_scanned (h_plain, if given, receives a copy of the bytes) */
     int32_t scan_frames;          /* with h_scan, AX.25 codecs only: the block was made with pm_scan_job.frames -> pm_codec_decode_framed */
+    int32_t scan_packets;         /* with h_scan, IL2P codecs only: the block was made with pm_scan_job.packets -> pm_codec_decode_packets */
 } pm_host_job;
 int pm_host_decode_batch(pm_host_job *jobs, int njobs, int threads);
 int pm_codec_fetch_batch(pm_codec *const *codecs, const int64_t *counts, int n, pm_packet *h_out, int threads);
@@ -648,7 +687,9 @@ int64_t pm_correlate_strided(void *h_records, int64_t stride, const int64_t *h_c
  * With the context's switch pipe_scan (pm_ctx_tune, PM_PIPE_SCAN; read by pm_pipe_create, default 0) the slicer threads run pm_stream_scan
  * behind pm_slice_compact, into the same block, and the host threads decode from its lists (pm_host_job.h_scan); results are the same.
  * The switch pipe_frames (PM_PIPE_FRAMES, default 0) implies pipe_scan and has the AX.25 chains' jobs write their frames too
- * (pm_scan_job.frames, pm_host_job.scan_frames); IL2P chains go the pipe_scan way.
+ * (pm_scan_job.frames, pm_host_job.scan_frames); IL2P chains go the pipe_scan way.  The switch pipe_packets (PM_PIPE_PACKETS, default 0),
+ * independent of pipe_frames, implies pipe_scan and has the IL2P chains' jobs make their attempts on the device (pm_scan_job.packets with the
+ * chain's codec options, pm_host_job.scan_packets).
  * Results equal process_chain on every chain + PacketMetaArray.Correlate, recording by recording.  One submitting thread.  The
  * device pointers inside the descs (taps) must stay valid for the pipeline's life; host arrays are copied by pm_pipe_create. */
 typedef struct pm_pipe_fir {         /* a sign-FIR group: sign(FIR(int16 audio)) as one bitmap (pm_fir_signs_i16) -- FSKModem.demod, fsk.py:149-159 */

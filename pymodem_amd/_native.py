@@ -85,13 +85,14 @@ class HostJob(ctypes.Structure):
                 ("lfsr_poly", ctypes.c_uint64), ("lfsr_state", ctypes.c_uint64), ("pending", ctypes.c_int64),
                 ("lfsr_invert", ctypes.c_int32), ("status", ctypes.c_int32),
                 ("h_addr_delta", ctypes.c_void_p), ("addr_first", ctypes.c_int64), ("h_plain", ctypes.c_void_p),
-                ("h_scan", ctypes.c_void_p), ("scan_frames", ctypes.c_int32)]
+                ("h_scan", ctypes.c_void_p), ("scan_frames", ctypes.c_int32), ("scan_packets", ctypes.c_int32)]
 
 
 class ScanJob(ctypes.Structure):
     """pm_scan_job"""
     _fields_ = [("d_data", ctypes.c_void_p), ("n", ctypes.c_int64), ("lfsr_poly", ctypes.c_uint64), ("lfsr_state", ctypes.c_uint64),
-                ("lfsr_invert", ctypes.c_int32), ("codec_kind", ctypes.c_int32), ("sync_tol", ctypes.c_int32), ("frames", ctypes.c_int32)]
+                ("lfsr_invert", ctypes.c_int32), ("codec_kind", ctypes.c_int32), ("sync_tol", ctypes.c_int32), ("frames", ctypes.c_int32),
+                ("packets", ctypes.c_int32), ("il2p_crc", ctypes.c_int32), ("il2p_disable_rs", ctypes.c_int32), ("il2p_min_dist", ctypes.c_int32)]
 
 
 SCAN_HEAD = 32        # PM_SCAN_HEAD
@@ -110,6 +111,22 @@ def scan_frame_table_bytes(n):
 def scan_frame_area_bytes(n):
     """PM_SCAN_FRAME_AREA_BYTES: the frame area, behind the table."""
     return (n + 7) // 8 * 8
+
+
+def scan_packet_table_bytes(n):
+    """PM_SCAN_PACKET_TABLE_BYTES: the packet table of a job with `packets` set, behind its descrambled bytes (padded to 8)."""
+    return 16 + 16 * (n // 64 + 2)
+
+
+def scan_packet_area_bytes(n):
+    """PM_SCAN_PACKET_AREA_BYTES: the packet area, behind the table."""
+    return (n + 7) // 8 * 8
+
+
+def scan_packet_dtype():
+    """NumPy view of a place of the packet table."""
+    import numpy as np
+    return np.dtype([("at", "<u4"), ("off", "<u4"), ("count", "<u2"), ("status", "u1"), ("corrected", "u1"), ("end", "<u4")])
 
 
 def scan_record_dtype():
@@ -319,6 +336,7 @@ _SIGS = {
     "pm_codec_decode": ([_vp, _vp, _vp, _i64, ctypes.POINTER(_i64)], _int),
     "pm_codec_decode_scanned": ([_vp, _vp, _vp, _i64, _vp, ctypes.POINTER(_i64)], _int),
     "pm_codec_decode_framed": ([_vp, _vp, _vp, _i64, _vp, ctypes.POINTER(_i64)], _int),
+    "pm_codec_decode_packets": ([_vp, _vp, _vp, _i64, _vp, ctypes.POINTER(_i64)], _int),
     "pm_codec_walked": ([_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)], _int),
     "pm_codec_fetch": ([_vp, _vp, _i64, ctypes.POINTER(_i64)], _int),
     "pm_host_decode_batch": ([ctypes.POINTER(HostJob), _int, _int], _int),

@@ -846,7 +846,7 @@ class NativePipeline:
     raises ValueError for anything else (use RecordingPipeline there)."""
 
     def __init__(self, chains, max_samples, address_distance, ctx=None, names=None, chain_ids=None, slots=0, slice_workers=0, slice_group=0,
-                 host_threads=0, decode_threads=0, slice_min_group=0, demod_streams=0, keep_slices=False, scan=False, frames=False):
+                 host_threads=0, decode_threads=0, slice_min_group=0, demod_streams=0, keep_slices=False, scan=False, frames=False, packets=False):
         import os
         demod_streams = demod_streams or int(os.environ.get("PYMODEM_AMD_PIPE_DEMOD_STREAMS", 0))
         slots = slots or int(os.environ.get("PYMODEM_AMD_PIPE_SLOTS", 0))              # tuning knobs (DESIGN.md 4.4b)
@@ -924,8 +924,9 @@ class NativePipeline:
         desc.keep_slices = int(bool(keep_slices))
         h = ctypes.c_void_p()
         # scan: the bitstream stage on the device (pm_stream_scan behind the slicers, the codecs decode from its lists).  pm_pipe_create
-        # reads the switch from its context.  frames: that, and the AX.25 chains' frames (de-stuffed bytes and CRC) come from the device too
-        on = {k: 1 for k, v in (("pipe_scan", scan), ("pipe_frames", frames)) if v}
+        # reads the switch from its context.  frames: that, and the AX.25 chains' frames (de-stuffed bytes and CRC) come from the device too.
+        # packets: that, and the IL2P chains' attempts (headers and RS blocks) are made on the device too
+        on = {k: 1 for k, v in (("pipe_scan", scan), ("pipe_frames", frames), ("pipe_packets", packets)) if v}
         ctx.tune(**on)
         try:
             check(lib().pm_pipe_create(ctx.handle, ctypes.byref(desc), ctypes.byref(h)))

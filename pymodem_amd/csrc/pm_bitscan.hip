@@ -11,9 +11,15 @@
 // Bits are handled in STREAM order: bit i of a word is stream bit 64 w + i (the bytes' bits from the top, as the slicer packs them).
 // With pm_scan_job.frames a fourth launch writes, for every listed flag, the frame it closes -- the de-stuffed bytes the decoder would have
 // collected since the flag in front, and their CRC-16 -- a wave per event, from a copy of the list that the emit launch leaves on the device.
+// With pm_scan_job.packets (IL2P) the emit launch lists the candidates {k, S} in context scratch and two more launches make the ATTEMPT
+// behind each (pm_il2p_core.h): the headers launch, a wave per job and a lane per candidate, decodes the 15 header bytes, counts out the
+// places in the packet area and finishes what ends with the header; the blocks launch, a fixed number of waves per job, decodes the payload
+// blocks of the placed ones -- syndromes, Chien search and descrambler across the lanes, Berlekamp and Forney on one -- and writes packet
+// and record.  Both read the slicer bytes and the scratch, never the block.
 #include "pm_common.h"
 #include "pm_bitscan_events.h"
 #include "pm_bitscan_frames.h"
+#include "pm_il2p_core.h"
 #include <algorithm>
 #include <cstring>
 
@@ -34,8 +40,15 @@ struct ScanJobs {
     int32_t njobs, tile_words;
     int64_t ev0[kScanJobs];                 // frames: the job's first place in the device-side copy of the lists, -1: no frames
     int32_t frame_words;
+    int32_t pk0[kScanJobs];                 // packets: the job's first place in the device-side candidate list, records and work list, -1: no packets
+    uint8_t pkopt[kScanJobs];               // packets: the codec's crc | disable_rs << 1 | min_dist (0 .. 9) << 2
+};
+struct PkRec {                              // the headers launch's copy of a record for the blocks launch, with the 13 descrambled header bytes
+    pm_il2p::Rec r;
+    uint8_t hdr[16];
 };
 constexpr int kFrameWaves = 256;            // waves that share a job's events in the frames launch (a wave a workgroup: the others leave at once)
+constexpr int kPacketWaves = 64;            // waves that share a job's placed records in the blocks launch
 constexpr uint32_t kClosesNothing = 0xFFFFFFFEu;   // F of the stream's first flag in the device-side copy when no frame ends there
 
 __device__ inline uint64_t load_word(const uint8_t *d, int64_t n, int64_t w)
@@ -61,6 +74,36 @@ __device__ inline uint64_t plain_word(const ScanJobs &J, int j, int64_t w, uint6
     }
     if (w == 0) o ^= J.reg0[j];             // bit t of the incoming register meets stream bit t
     return J.invert[j] ? ~o : o;
+}
+
+// the descrambled stream's word w (zeros outside the stream), and 64 / 32 of its bits from any bit B on, the first in bit 0
+__device__ inline uint64_t stream_word(const ScanJobs &J, int j, int64_t n, int64_t w)
+{
+    if (w < 0 || 8 * w >= n) return 0;
+    return plain_word(J, j, w, load_word(J.data[j], n, w), load_word(J.data[j], n, w - 1));
+}
+__device__ inline uint64_t stream_bits64(const ScanJobs &J, int j, int64_t n, int64_t B)
+{
+    const int64_t w = B >> 6;
+    const int s = (int)(B & 63);
+    const uint64_t lo = stream_word(J, j, n, w);
+    return s ? (lo >> s) | (stream_word(J, j, n, w + 1) << (64 - s)) : lo;
+}
+__device__ inline unsigned stream_byte(uint64_t bits, int q) { return __brev((unsigned)(bits >> (8 * q)) & 0xFFu) >> 24; }     // byte q of them, its first bit on top
+
+// il2p.py:367-376 at the eight bit offsets of byte b of a word: bit s set where the 32 bits that end at offset s hit.  C, P: the word and the
+// one in front, most significant bit first (byte 0 on top)
+__device__ inline unsigned il2p_byte_hits(uint64_t C, uint64_t P, int b, int tol)
+{
+    const int sh = 8 * (7 - b);
+    const uint64_t win = (sh ? (C >> sh) | (P << (64 - sh)) : C) & 0xFFFFFFFFFFull;
+    unsigned hits = 0;
+    for (int s = 0; s < 8; ++s) {
+        const uint32_t v = (uint32_t)(win >> (7 - s));
+        // (__popc is unsigned: compared as such, a tol of -1 would let every byte through)
+        hits |= (unsigned)((int)__popc((v & 0xFFFFFFu) ^ 0xF15E48u) <= tol || (int)__popc(v ^ 0x5D57DF7Fu) <= tol) << s;
+    }
+    return hits;
 }
 
 template <class T, class Op>
@@ -154,15 +197,7 @@ __global__ __launch_bounds__(kLanes) void bitscan_tile_kernel(ScanJobs J, uint8_
             for (int b = 0; b < 8; ++b) {
                 const int64_t k = 8 * w + b;
                 if (k < 4 || k >= n) continue;
-                const int sh = 8 * (7 - b);
-                const uint64_t win = (sh ? (C >> sh) | (P << (64 - sh)) : C) & 0xFFFFFFFFFFull;
-                bool hit = false;
-                for (int s = 0; s < 8; ++s) {
-                    const uint32_t v = (uint32_t)(win >> (7 - s));
-                    // (__popc is unsigned: compared as such, a tol of -1 would let every byte through)
-                    hit = hit || (int)__popc((v & 0xFFFFFFu) ^ 0xF15E48u) <= tol || (int)__popc(v ^ 0x5D57DF7Fu) <= tol;
-                }
-                bits |= (unsigned)hit << b;
+                bits |= (unsigned)(il2p_byte_hits(C, P, b, tol) != 0) << b;
             }
             list[w] = (uint8_t)bits;
             if (w == nw - 1)
@@ -201,8 +236,9 @@ __global__ __launch_bounds__(64) void bitscan_combine_kernel(ScanJobs J, uint8_t
         for (int l = 0; l < 64 && r0 + l < nt; ++l) {
             const TileSum of{__shfl(s.dropped, l), __shfl(s.first_reset, l), __shfl(s.dropped_to_first, l), __shfl(s.last_reset, l), __shfl(s.dropped_after_last, l),
                              __shfl(s.first_flag, l), __shfl(s.last_flag, l), __shfl(s.closing, l), __shfl(s.bail, l), __shfl(s.bits, l), {0, 0}};
+            TileCarry c = kind == 0 ? combine_step(st, of, (int64_t)(r0 + l) * tw * 64) : combine_carry(st);
+            if (kind == 1) c.events = cands;                // an IL2P tile: the candidates in front of it
             cands += of.closing;
-            const TileCarry c = kind == 0 ? combine_step(st, of, (int64_t)(r0 + l) * tw * 64) : combine_carry(st);
             if (l == lane) mine = c;
         }
         if (r0 + lane < nt) carries[t0 + r0 + lane] = mine;
@@ -220,16 +256,42 @@ __global__ __launch_bounds__(64) void bitscan_combine_kernel(ScanJobs J, uint8_t
         *reinterpret_cast<int64_t *>(rec + 16) = kind == 0 ? r.last_flag : -1;
         *reinterpret_cast<int32_t *>(rec + 24) = kind == 0 ? r.events : 0;
         *reinterpret_cast<int32_t *>(rec + 28) = kind == 1 ? cands : 0;
-        if (counts) counts[j] = kind == 0 ? r.events : 0;      // for the frames launch: the block may be host memory, nothing is read back from it
+        if (counts) counts[j] = kind == 0 ? r.events : kind == 1 ? cands : 0;      // for the frames and packets launches: the block may be host memory, nothing is read back from it
     }
 }
 
-// Launch 3: the events of every AX.25 tile, at the places the combine counted out.
-__global__ __launch_bounds__(kLanes) void bitscan_emit_kernel(ScanJobs J, uint8_t *block, const TileCarry *carries, uint2 *copies)
+// Launch 3: the events of every AX.25 tile, at the places the combine counted out; packets: the candidates {k, S} of every IL2P tile likewise,
+// into the device-side list.
+__global__ __launch_bounds__(kLanes) void bitscan_emit_kernel(ScanJobs J, uint8_t *block, const TileCarry *carries, uint2 *copies, uint32_t *cands)
 {
     __shared__ Seg lds[kLanes];
     __shared__ int32_t cnt[kLanes];
     const int tile = blockIdx.x, j = job_of_tile(J, tile), tw = J.tile_words;
+    if (J.kind[j] == 1 && J.pk0[j] >= 0) {
+        const int64_t n = J.n[j], nw = (n + 7) / 8, w = (int64_t)(tile - J.tile0[j]) * tw + threadIdx.x, places = n / 64 + 2;
+        unsigned bits = 0, offs = 0;                        // the word's candidate bytes, and the smallest offset that hits in each (3 bits a byte)
+        if ((int)threadIdx.x < tw && w < nw) {
+            const uint8_t *d = J.data[j];
+            const uint64_t i0 = load_word(d, n, w), i1 = load_word(d, n, w - 1), i2 = load_word(d, n, w - 2);
+            const uint64_t C = __brevll(plain_word(J, j, w, i0, i1) & valid_bits(n, w)), P = __brevll(w ? plain_word(J, j, w - 1, i1, i2) : 0);
+            for (int b = 0; b < 8; ++b) {
+                const int64_t k = 8 * w + b;
+                if (k < 4 || k >= n) continue;
+                const unsigned hits = il2p_byte_hits(C, P, b, J.tol[j]);
+                if (hits) {
+                    bits |= 1u << b;
+                    offs |= (unsigned)__builtin_ctz(hits) << (3 * b);
+                }
+            }
+        }
+        block_scan((int32_t)__popc(bits), cnt, [](int32_t a, int32_t b) { return a + b; });
+        int64_t at = (int64_t)carries[tile].events + (threadIdx.x ? cnt[threadIdx.x - 1] : 0);
+        for (unsigned m = bits; m; m &= m - 1, ++at) {
+            const int b = __builtin_ctz(m);
+            if (at < places) cands[J.pk0[j] + at] = (uint32_t)((8 * w + b) << 3) | ((offs >> (3 * b)) & 7u);
+        }
+        return;
+    }
     if (J.kind[j] != 0) return;
     const TileCarry c = carries[tile];
     if (c.events < 0) return;
@@ -388,6 +450,189 @@ __global__ __launch_bounds__(64) void bitscan_frames_kernel(ScanJobs J, uint8_t 
     }
 }
 
+// Launch 5 (pm_scan_job.packets): a wave per job takes its candidates 64 at a time, a lane a candidate: the 15 header bytes from bit H, RS(2),
+// the descrambler, the count, where the attempt would end (pm_il2p::header_attempt).  A scan over the lanes, carried from trip to trip, gives
+// every passed and complete header its place in the area in candidate order; from the first that does not fit on, none is placed.  What ends
+// here -- INCOMPLETE, HEADER_FAIL, NOT_PLACED, DONE without payload -- goes to the table at once; every record is copied to scratch, and the
+// placed ones with payload are listed there for the blocks launch.
+__global__ __launch_bounds__(64) void bitscan_headers_kernel(ScanJobs J, uint8_t *block, const int32_t *counts, const uint32_t *cands, PkRec *recs, int32_t *work,
+                                                             int32_t *pkcounts)
+{
+    using namespace pm_il2p;
+    using pm_frames::low_mask;
+    __shared__ GF256 g;
+    const int j = blockIdx.x, lane = threadIdx.x;
+    if (J.pk0[j] < 0) return;
+    if (lane == 0) gf_build(&g);
+    __syncthreads();
+    const int64_t n = J.n[j], places = n / 64 + 2, area_bytes = PM_SCAN_PACKET_AREA_BYTES(n);
+    const int32_t records = (int32_t)(counts[j] < places ? counts[j] : places), base = J.pk0[j];
+    uint8_t *table = block + J.off[j] + PM_SCAN_HEAD + list_bytes(1, n) + ((n + 7) & ~int64_t(7)), *area = table + PM_SCAN_PACKET_TABLE_BYTES(n);
+    const Opts o{J.pkopt[j] & 1, (J.pkopt[j] >> 1) & 1, J.pkopt[j] >> 2};
+    int64_t used = 0;                                       // bytes of the area counted out so far
+    int32_t nwork = 0, nplaced = 0;
+    bool full = false;
+    for (int32_t r0 = 0; r0 < records; r0 += 64) {
+        const int32_t e = r0 + lane;
+        const bool active = e < records;
+        PkRec pr;
+        for (int q = 0; q < 16; ++q) pr.hdr[q] = 0;
+        pr.r = rec_incomplete(0);
+        uint32_t need = 0;
+        if (active) {
+            const uint32_t at = cands[base + e];
+            const int64_t H = rec_H(at);
+            pr.r = rec_incomplete(at);
+            if (H + kHeaderBits <= 8 * n) {
+                const uint64_t b0 = stream_bits64(J, j, n, H), b1 = stream_bits64(J, j, n, H + 64);
+                for (int q = 0; q < 8; ++q) pr.hdr[q] = (uint8_t)stream_byte(b0, q);
+                for (int q = 0; q < 7; ++q) pr.hdr[8 + q] = (uint8_t)stream_byte(b1, q);
+                pr.r = header_attempt(&g, at, pr.hdr, o, 8 * n);
+                if (pr.r.status == kDone) need = rec_need(pr.r.count);
+            }
+        }
+        uint32_t upto = need;                               // inclusive over the lanes
+        for (int dl = 1; dl < 64; dl <<= 1) {
+            const uint32_t v = __shfl_up(upto, dl);
+            if (lane >= dl) upto += v;
+        }
+        const int64_t off = used + upto - need;
+        const uint64_t over = __ballot(need && off + need > area_bytes);
+        const bool placed = need && !full && !(over && lane >= __builtin_ctzll(over));
+        const uint64_t with_blocks = __ballot(placed && pr.r.count > 0);
+        if (placed) pr.r.off = (uint32_t)off;
+        else if (need) pr.r = rec_not_placed(pr.r);
+        if (active) {
+            if (placed && pr.r.count > 0) work[base + nwork + __popcll(with_blocks & low_mask(lane))] = e;
+            recs[base + e] = pr;
+            if (!(placed && pr.r.count > 0)) {
+                uint2 *place = reinterpret_cast<uint2 *>(table + 16 + 16 * (int64_t)e);
+                place[0] = make_uint2(pr.r.at, pr.r.off);
+                place[1] = make_uint2((uint32_t)pr.r.count | (uint32_t)pr.r.status << 16 | (uint32_t)pr.r.corrected << 24, pr.r.end);
+                if (placed) {                               // a packet of its header alone: 13 bytes and three zeros
+                    uint64_t v0 = 0, v1 = 0;
+                    for (int q = 0; q < 8; ++q) v0 |= (uint64_t)pr.hdr[q] << (8 * q);
+                    for (int q = 0; q < 5; ++q) v1 |= (uint64_t)pr.hdr[8 + q] << (8 * q);
+                    uint64_t *dst = reinterpret_cast<uint64_t *>(area + off);
+                    dst[0] = v0;
+                    dst[1] = v1;
+                }
+            }
+        }
+        used += __shfl(upto, 63);
+        nwork += __popcll(with_blocks);
+        nplaced += __popcll(__ballot(placed));
+        full = full || over != 0;
+    }
+    if (lane == 0) {
+        uint2 *head = reinterpret_cast<uint2 *>(table);
+        head[0] = make_uint2((uint32_t)records, (uint32_t)nplaced);
+        head[1] = make_uint2(0u, 0u);
+        pkcounts[2 * j] = records;
+        pkcounts[2 * j + 1] = nwork;
+    }
+}
+
+// Launch 6 (pm_scan_job.packets): wave x of a job takes the work list's records x, x + waves, ...: the placed records with payload.  Per block:
+// the lanes load the block's bytes at its bit offset, four a lane, into LDS; each lane's share of the 16 syndromes (pm_il2p::syn_segment),
+// XORed over the wave; if any is set, Berlekamp on lane 0, the Chien search a position per lane, Forney on lane 0, and the syndromes again;
+// the descrambler a byte per lane into the packet, which is put together in LDS behind its 13 header bytes and goes out in whole words once
+// every block has passed.  The wave writes the record whole at the end.
+__global__ __launch_bounds__(64) void bitscan_blocks_kernel(ScanJobs J, uint8_t *block, const PkRec *recs, const int32_t *work, const int32_t *pkcounts)
+{
+    using namespace pm_il2p;
+    using pm_frames::low_mask;
+    __shared__ GF256 g;
+    __shared__ uint32_t buf32[64], pkt32[264];              // a block of up to 255 bytes; the packet: 13 + 1023 bytes, padded to 8
+    __shared__ int syn[16], loc[17], where[17];
+    const int j = blockIdx.y, lane = threadIdx.x;
+    if (J.pk0[j] < 0) return;
+    if (lane == 0) gf_build(&g);
+    __syncthreads();
+    const int64_t n = J.n[j];
+    const int32_t nwork = pkcounts[2 * j + 1], base = J.pk0[j];
+    uint8_t *table = block + J.off[j] + PM_SCAN_HEAD + list_bytes(1, n) + ((n + 7) & ~int64_t(7)), *area = table + PM_SCAN_PACKET_TABLE_BYTES(n);
+    const bool disable_rs = (J.pkopt[j] >> 1) & 1;
+    const int min_dist = J.pkopt[j] >> 2;
+    uint8_t *buf = reinterpret_cast<uint8_t *>(buf32), *pkt = reinterpret_cast<uint8_t *>(pkt32);
+    // the wave's syndromes of the nb bytes in buf, four to a word, the same in every lane
+    auto syndromes = [&](int nb, uint32_t *s4) {
+        int cnt = nb - 4 * lane;
+        cnt = cnt < 0 ? 0 : cnt > 4 ? 4 : cnt;
+        const uint32_t mine = buf32[lane];
+        const uint8_t seg[4] = {(uint8_t)mine, (uint8_t)(mine >> 8), (uint8_t)(mine >> 16), (uint8_t)(mine >> 24)};
+        const int tail = nb - 4 * lane - cnt;
+        for (int q = 0; q < 4; ++q) {
+            uint32_t v = 0;
+            if (cnt)
+                for (int i = 0; i < 4; ++i) v |= syn_segment(&g, 4 * q + i, seg, cnt, tail) << (8 * i);
+            for (int dl = 32; dl; dl >>= 1) v ^= __shfl_xor(v, dl);
+            s4[q] = v;
+        }
+    };
+    for (int32_t wi = (int32_t)blockIdx.x; wi < nwork; wi += (int32_t)gridDim.x) {
+        const int32_t e = work[base + wi];
+        const PkRec pr = recs[base + e];
+        const int count = pr.r.count;
+        const Split split = block_split(count);
+        const int need = (int)rec_need(count);
+        __syncthreads();
+        for (int v = lane; v < need / 4; v += 64) pkt32[v] = 0;
+        __syncthreads();
+        if (lane < 13) pkt[lane] = pr.hdr[lane];
+        int corrected = pr.r.corrected, appended = 0;
+        uint32_t end = (uint32_t)kHeaderBits;
+        bool fail = false;
+        for (int b = 0; b < split.blocks && !fail; ++b) {
+            const int bs = block_bytes(split, b), nb = bs + 16;
+            __syncthreads();
+            {
+                const uint32_t v = 4 * lane < nb ? (uint32_t)stream_bits64(J, j, n, rec_H(pr.r.at) + end + 32 * lane) : 0u;
+                buf32[lane] = stream_byte(v, 0) | stream_byte(v, 1) << 8 | stream_byte(v, 2) << 16 | stream_byte(v, 3) << 24;
+            }
+            __syncthreads();
+            int fixed = 0;
+            uint32_t s4[4] = {0, 0, 0, 0};
+            if (!disable_rs) syndromes(nb, s4);
+            if (!disable_rs && (s4[0] | s4[1] | s4[2] | s4[3])) {
+                if (lane == 0) {
+                    for (int i = 0; i < 16; ++i) syn[i] = (int)((s4[i >> 2] >> (8 * (i & 3))) & 0xFF);
+                    rs_berlekamp(&g, 16, syn, loc);
+                }
+                __syncthreads();
+                for (int t = 0; t < 4; ++t) {               // a position per lane, in ascending order
+                    const int pos = 64 * t + lane;
+                    const bool root = pos < nb && rs_chien_at(&g, 16, loc, nb, pos) == 0;
+                    const uint64_t m = __ballot(root);
+                    const int idx = fixed + __popcll(m & low_mask(lane));
+                    if (root && idx < 17) where[idx] = pos;
+                    fixed += __popcll(m);
+                }
+                __syncthreads();
+                if (lane == 0 && fixed <= 8 - min_dist) rs_forney(&g, 16, syn, loc, where, fixed, nb, buf);
+                __syncthreads();
+                syndromes(nb, s4);
+                fail = (s4[0] | s4[1] | s4[2] | s4[3]) != 0;
+            }
+            end += 8u * (uint32_t)nb;
+            if (fail) break;
+            corrected += fixed;
+            for (int k = lane; k < bs; k += 64) pkt[13 + appended + k] = (uint8_t)descramble_at(buf[k], k >= 1 ? buf[k - 1] : 0u, k >= 2 ? buf[k - 2] : 0u, k);
+            appended += bs;
+        }
+        __syncthreads();
+        if (!fail) {
+            uint64_t *dst = reinterpret_cast<uint64_t *>(area + pr.r.off);
+            for (int v = lane; v < need / 8; v += 64) dst[v] = pkt32[2 * v] | (uint64_t)pkt32[2 * v + 1] << 32;
+        }
+        if (lane == 0) {
+            uint2 *place = reinterpret_cast<uint2 *>(table + 16 + 16 * (int64_t)e);
+            place[0] = make_uint2(pr.r.at, pr.r.off);
+            place[1] = make_uint2((uint32_t)count | (uint32_t)(fail ? kBlockFail : kDone) << 16 | (uint32_t)corrected << 24, end);
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int pm_stream_scan(pm_ctx *ctx, const pm_scan_job *h_jobs, int njobs, void *d_block, size_t block_bytes, int64_t *h_offsets, size_t *h_used)
@@ -402,12 +647,13 @@ extern "C" int pm_stream_scan(pm_ctx *ctx, const pm_scan_job *h_jobs, int njobs,
     const int ftune = ctx->tune.bitscan_frame_words;
     J.frame_words = ftune > 0 ? std::min(ftune, 64) : 64;
     size_t at = 0;
-    int64_t tiles = 0, copies = 0;
+    int64_t tiles = 0, copies = 0, places = 0;
     for (int j = 0; j < njobs; ++j) {
         const pm_scan_job &q = h_jobs[j];
         PM_ARG(q.n >= 0 && q.n <= (int64_t)1 << 29 && (q.n == 0 || (q.d_data && ((uintptr_t)q.d_data & 7) == 0)));
         PM_ARG(q.codec_kind >= -1 && q.codec_kind <= 1);
         PM_ARG(q.frames == 0 || (q.frames == 1 && q.codec_kind == 0));
+        PM_ARG(q.packets == 0 || (q.packets == 1 && q.codec_kind == 1));
         J.data[j] = q.d_data;
         J.poly[j] = q.lfsr_poly;
         J.reg0[j] = q.lfsr_state;
@@ -424,6 +670,14 @@ extern "C" int pm_stream_scan(pm_ctx *ctx, const pm_scan_job *h_jobs, int njobs,
             J.ev0[j] = copies;
             copies += q.n / 19 + 2;
         }
+        J.pk0[j] = -1;
+        if (q.packets) {
+            at += (size_t)PM_SCAN_PACKET_TABLE_BYTES(q.n) + (size_t)PM_SCAN_PACKET_AREA_BYTES(q.n);
+            J.pk0[j] = (int32_t)places;
+            // (a min_dist below 0 corrects what 0 does, one above 8 nothing: the locator has eight roots at most)
+            J.pkopt[j] = (uint8_t)((q.il2p_crc != 0) | (q.il2p_disable_rs != 0) << 1 | std::max(0, std::min(9, q.il2p_min_dist)) << 2);
+            places += q.n / 64 + 2;
+        }
         tiles += pm_cdiv(pm_cdiv(q.n, 8), J.tile_words);
         PM_ARG(tiles < (int64_t)1 << 30);
     }
@@ -432,19 +686,31 @@ extern "C" int pm_stream_scan(pm_ctx *ctx, const pm_scan_job *h_jobs, int njobs,
     if (at > block_bytes) return pm_set_error(PM_ERR_CAPACITY, "pm_stream_scan: the block holds %zu bytes, the batch needs %zu", block_bytes, at);
     const size_t sums_bytes = ((size_t)tiles * sizeof(TileSum) + 63) & ~(size_t)63;
     // (frames: the event counts and a copy of the lists stay on the device for the frames launch, behind the carries)
-    const size_t carries_bytes = ((size_t)tiles * sizeof(TileCarry) + 63) & ~(size_t)63, counts_bytes = copies ? kScanJobs * sizeof(int32_t) : 0;
-    if (int rc = pm_scratch_reserve(ctx, sums_bytes + carries_bytes + counts_bytes + (size_t)copies * sizeof(uint2) + 64)) return rc;
+    const size_t carries_bytes = ((size_t)tiles * sizeof(TileCarry) + 63) & ~(size_t)63, counts_bytes = copies || places ? kScanJobs * sizeof(int32_t) : 0;
+    // (packets: the candidates, a copy of every record with its header bytes, the list of those with blocks to decode, and the two counts per job)
+    const size_t lists_bytes = (size_t)copies * sizeof(uint2), cands_bytes = ((size_t)places * sizeof(uint32_t) + 63) & ~(size_t)63, recs_bytes = (size_t)places * sizeof(PkRec);
+    const size_t pk_bytes = places ? 2 * cands_bytes + recs_bytes + 2 * kScanJobs * sizeof(int32_t) : 0;
+    if (int rc = pm_scratch_reserve(ctx, sums_bytes + carries_bytes + counts_bytes + lists_bytes + pk_bytes + 128)) return rc;
     TileSum *sums = static_cast<TileSum *>(ctx->d_scratch);
     TileCarry *carries = reinterpret_cast<TileCarry *>(static_cast<uint8_t *>(ctx->d_scratch) + sums_bytes);
-    int32_t *counts = copies ? reinterpret_cast<int32_t *>(static_cast<uint8_t *>(ctx->d_scratch) + sums_bytes + carries_bytes) : nullptr;
+    int32_t *counts = copies || places ? reinterpret_cast<int32_t *>(static_cast<uint8_t *>(ctx->d_scratch) + sums_bytes + carries_bytes) : nullptr;
     uint2 *lists = reinterpret_cast<uint2 *>(static_cast<uint8_t *>(ctx->d_scratch) + sums_bytes + carries_bytes + counts_bytes);
+    uint8_t *pk = reinterpret_cast<uint8_t *>(((uintptr_t)lists + lists_bytes + 63) & ~(uintptr_t)63);
+    uint32_t *cands = reinterpret_cast<uint32_t *>(pk);
+    int32_t *work = reinterpret_cast<int32_t *>(pk + cands_bytes), *pkcounts = reinterpret_cast<int32_t *>(pk + 2 * cands_bytes);
+    PkRec *recs = reinterpret_cast<PkRec *>(pk + 2 * cands_bytes + 2 * kScanJobs * sizeof(int32_t));
     uint8_t *block = static_cast<uint8_t *>(d_block);
     if (tiles) hipLaunchKernelGGL(bitscan_tile_kernel, dim3((unsigned)tiles), dim3(kLanes), 0, ctx->stream, J, block, sums);
     hipLaunchKernelGGL(bitscan_combine_kernel, dim3(njobs), dim3(64), 0, ctx->stream, J, block, sums, carries, counts);
     bool any = false;
-    for (int j = 0; j < njobs; ++j) any = any || (h_jobs[j].codec_kind == 0 && h_jobs[j].n > 0);
-    if (any) hipLaunchKernelGGL(bitscan_emit_kernel, dim3((unsigned)tiles), dim3(kLanes), 0, ctx->stream, J, block, carries, lists);
+    for (int j = 0; j < njobs; ++j) any = any || ((h_jobs[j].codec_kind == 0 || h_jobs[j].packets) && h_jobs[j].n > 0);
+    if (any) hipLaunchKernelGGL(bitscan_emit_kernel, dim3((unsigned)tiles), dim3(kLanes), 0, ctx->stream, J, block, carries, lists, cands);
     if (copies) hipLaunchKernelGGL(bitscan_frames_kernel, dim3(kFrameWaves, njobs), dim3(64), 0, ctx->stream, J, block, lists, counts);
+    if (places) {
+        const int ptune = ctx->tune.bitscan_packet_waves;
+        hipLaunchKernelGGL(bitscan_headers_kernel, dim3(njobs), dim3(64), 0, ctx->stream, J, block, counts, cands, recs, work, pkcounts);
+        hipLaunchKernelGGL(bitscan_blocks_kernel, dim3(ptune > 0 ? std::min(ptune, 1024) : kPacketWaves, njobs), dim3(64), 0, ctx->stream, J, block, recs, work, pkcounts);
+    }
     PM_HIP(hipGetLastError());
     return PM_OK;
 }

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/pymodem_amd.h"
+#include "pm_il2p_core.h"
 
 int pm_set_error(int code, const char *fmt, ...);
 
@@ -101,158 +102,45 @@ struct Sink {
     }
 };
 
-// ---- GF(2^8) / Reed-Solomon ----------------------------------------------------------------------
-struct GF256 {
-    int table[255], index[256], inverse[256];
-    GF256()
-    {
-        // gf_functions.py:47-74: a Galois LFSR stepped from a^0, filling the table from the top down
-        unsigned reg = 1;
-        memset(index, 0, sizeof(index));
-        for (int i = 254; i >= 0; --i) {
-            const unsigned fb = reg & 1;
-            reg >>= 1;
-            if (fb) reg ^= 0x11D >> 1;
-            table[i] = (int)reg;
-            index[reg] = i;
-        }
-        inverse[0] = 0;
-        for (int i = 1; i < 256; ++i) {
-            int j = 1;
-            while (mul(i, j) != 1) ++j;
-            inverse[i] = j;
-        }
-    }
-    int mul(int a, int b) const
-    {
-        if (a == 0 || b == 0) return 0;
-        int r = index[a] + index[b];
-        while (r > 254) r -= 255;
-        return table[r];
-    }
+// ---- GF(2^8) / Reed-Solomon: pm_il2p_core.h, shared with pm_stream_scan's packets launches ------------------------------------
+struct HostGF : pm_il2p::GF256 {
     // row[i][v] = v * table[i] for the 16 generator roots table[0..15]: one lookup per byte in the Horner syndromes
     uint8_t row[16][256];
-    void build_rows()
+    HostGF()
     {
+        pm_il2p::gf_build(this);
         for (int i = 0; i < 16; ++i)
-            for (int v = 0; v < 256; ++v) row[i][v] = (uint8_t)mul(v, table[i]);
+            for (int v = 0; v < 256; ++v) row[i][v] = (uint8_t)pm_il2p::gf_mul(this, v, table[i]);
     }
 };
 
-const GF256 &gf()
+const HostGF &gf()
 {
-    static const GF256 g = [] { GF256 t; t.build_rows(); return t; }();
+    static const HostGF g;
     return g;
-}
-
-int wrap255(int x)
-{
-    while (x > 254) x -= 255;
-    return x;
 }
 
 // rs_functions.py:33-150 (first_root is 0 for both IL2P codes).  Corrects buf[0..n) in place.
 int rs_decode(int num_roots, uint8_t *buf, int n, int min_distance)
 {
-    const GF256 &g = gf();
-    const int first_root = 0, half = num_roots / 2;
-    int syn[16];
-    auto syndromes = [&]() {
+    const HostGF &g = gf();
+    return pm_il2p::rs_decode(&g, num_roots, buf, n, min_distance, [&](const uint8_t *b, int len, int *syn) {
         // Horner in every root at once: byte by byte, the roots' chains side by side (each step of one chain is a table lookup that
         // waits for the one before it: root by root that was 16 x n dependent loads, 2 us for a 100-byte block)
         unsigned v[16] = {0};
         if (num_roots == 16) {
-            for (int j = 0; j < n - 1; ++j) {
-                const unsigned b = buf[j];
-                for (int i = 0; i < 16; ++i) v[i] = g.row[first_root + i][v[i] ^ b];     // row[i]: multiplication by the i-th root
+            for (int j = 0; j < len - 1; ++j) {
+                const unsigned x = b[j];
+                for (int i = 0; i < 16; ++i) v[i] = g.row[i][v[i] ^ x];     // row[i]: multiplication by the i-th root
             }
         } else {
-            for (int j = 0; j < n - 1; ++j) {
-                const unsigned b = buf[j];
-                for (int i = 0; i < num_roots; ++i) v[i] = g.row[first_root + i][v[i] ^ b];
+            for (int j = 0; j < len - 1; ++j) {
+                const unsigned x = b[j];
+                for (int i = 0; i < num_roots; ++i) v[i] = g.row[i][v[i] ^ x];
             }
         }
-        for (int i = 0; i < num_roots; ++i) syn[i] = (int)(v[i] ^ buf[n - 1]);
-    };
-    syndromes();
-    {
-        // All syndromes zero: the locator stays {1}, the Chien search finds no root (x = loc[0] = 1), nothing is corrected and
-        // the closing check passes -- the reference's algorithm returns 0 with the data untouched.  Skip straight there.
-        bool clean = true;
-        for (int i = 0; i < num_roots; ++i) clean &= syn[i] == 0;
-        if (clean) return 0;
-    }
-    int loc[17] = {0}, nxt[17] = {0}, corr[18] = {0}, where[17] = {0};
-    loc[0] = 1;
-    corr[1] = 1;
-    int order = 0;
-    for (int step = 1; step <= num_roots; ++step) {          // Berlekamp
-        const int y = step - 1;
-        int e = syn[y];
-        for (int i = 1; i <= order; ++i) e ^= g.mul(loc[i], syn[y - i]);
-        if (e != 0) {
-            for (int i = 0; i <= order; ++i) nxt[i] = loc[i] ^ g.mul(e, corr[i]);
-            e = g.inverse[e];
-            for (int i = 0; i <= half; ++i) corr[i] = g.mul(loc[i], e);
-            for (int i = 0; i <= half; ++i) loc[i] = nxt[i];
-        }
-        if (2 * order < step) order = step - order;
-        for (int i = num_roots; i > 0; --i) corr[i] = corr[i - 1];
-        corr[0] = 0;
-    }
-    int count = 0;
-    // Chien search.  The exponent of term i at position j is ((j + 256 - n) i + index[loc[i]]) mod 255: kept per term and advanced by i
-    // from one position to the next instead of being reduced from scratch (wrap255 subtracts 255 up to eight times per term)
-    int ex[9], ni = 0, which[9];
-    for (int i = 1; i <= half; ++i)
-        if (loc[i]) {
-            ex[ni] = wrap255((256 - n) * i + g.index[loc[i]]);
-            which[ni++] = i;
-        }
-    for (int j = 0; j < n; ++j) {
-        int x = 0;
-        for (int k = 0; k < ni; ++k) {
-            x ^= g.table[ex[k]];
-            ex[k] += which[k];
-            if (ex[k] > 254) ex[k] -= 255;
-        }
-        x ^= loc[0];
-        if (x == 0) {
-            if (count < 17) where[count] = j;
-            ++count;
-        }
-    }
-    if (count <= half - min_distance) {                      // Forney
-        for (int i = 0; i < count; ++i) {
-            corr[i] = syn[first_root + i];
-            for (int j = 1; j <= i; ++j) corr[i] ^= g.mul(syn[first_root + i - j], loc[j]);
-        }
-        for (int i = 0; i < count; ++i) {
-            const int e = n - where[i] - 1;
-            int z = corr[0];
-            for (int j = 1; j < count; ++j) {
-                int x = wrap255(e * j);
-                x = wrap255(256 - x - 1);
-                z ^= g.mul(corr[j], g.table[x]);
-            }
-            z = g.mul(z, g.table[e]);
-            int y = loc[1];
-            for (int j = 3; j <= half; j += 2) {
-                int x = wrap255(e * (j - 1));
-                x = wrap255(256 - x - 1);
-                y ^= g.mul(loc[j], g.table[x]);
-            }
-            y = g.index[y];
-            y = 256 - y - 1;
-            if (y == 255) y = 0;
-            y = g.table[y];
-            buf[where[i]] ^= (uint8_t)g.mul(y, z);
-        }
-    }
-    syndromes();
-    for (int i = 0; i < num_roots; ++i)
-        if (syn[i] != 0) return -1;
-    return count;
+        for (int i = 0; i < num_roots; ++i) syn[i] = (int)(v[i] ^ b[len - 1]);
+    });
 }
 
 }  // namespace
@@ -270,6 +158,8 @@ struct pm_codec {
     virtual bool feed_scanned(const uint8_t *d, const int64_t *a, int64_t n, const uint8_t *scan) = 0;
     // the same with the frame table and the frame area of a block made with pm_scan_job.frames (AX.25 only)
     virtual bool feed_framed(const uint8_t *, const int64_t *, int64_t, const uint8_t *) { return false; }
+    // the same with the packet table and the packet area of a block made with pm_scan_job.packets (IL2P only)
+    virtual bool feed_packets(const uint8_t *, const int64_t *, int64_t, const uint8_t *) { return false; }
     virtual void feed(uint8_t byte, int64_t addr, Sink &sink) = 0;
     virtual void feed_many(const uint8_t *d, const int64_t *a, int64_t n)
     {
@@ -704,6 +594,88 @@ struct Il2p : pm_codec {
         return true;
     }
 
+    // pm_stream_scan's packet table (its places) and packet area while feed_packets runs: what feed_search looks a hit up in
+    const uint8_t *pk_places = nullptr, *pk_area = nullptr;
+    int32_t pk_records = 0, pk_cursor = 0;
+
+    // feed_search with the records of the attempts that the device has made (pm_il2p_core.h, include/pymodem_amd.h): a hit of the decoder's
+    // own register test whose record says what the attempt from there comes to is not walked.  false: the table cannot belong to the stream.
+    bool feed_packets(const uint8_t *d, const int64_t *a, int64_t n, const uint8_t *scan) override
+    {
+        using namespace pm_il2p;
+        const uint8_t *table = scan + PM_SCAN_HEAD + PM_SCAN_LIST_BYTES(1, n) + ((n + 7) & ~int64_t(7)), *area = table + PM_SCAN_PACKET_TABLE_BYTES(n);
+        int32_t records, placed;
+        memcpy(&records, table, 4);
+        memcpy(&placed, table + 4, 4);
+        if (records < 0 || records > n / 64 + 2 || placed < 0 || placed > records) return false;
+        int64_t last_k = -1;
+        for (int32_t e = 0; e < records; ++e) {
+            Rec r;
+            memcpy(&r, table + 16 + 16 * (int64_t)e, 16);
+            const int64_t k = r.at >> 3, H = rec_H(r.at);
+            if (k <= last_k || k < 4 || k >= n || r.count > 1023 || r.status > kNotPlaced) return false;
+            last_k = k;
+            if (r.status == kHeaderFail && H + kHeaderBits > 8 * n) return false;
+            if (r.status == kDone || r.status == kBlockFail) {
+                if (r.end < (uint32_t)kHeaderBits || H + r.end + (r.status == kDone && want_crc ? 32 : 0) > 8 * n) return false;
+                if ((r.off & 7) || (int64_t)r.off + rec_need(r.count) > PM_SCAN_PACKET_AREA_BYTES(n)) return false;
+                if (r.status == kDone && (header_count(area + r.off) != r.count || r.end != kHeaderBits + body_bits(r.count))) return false;
+            }
+        }
+        pk_places = table + 16;
+        pk_area = area;
+        pk_records = records;
+        pk_cursor = 0;
+        feed_search(d, a, n, scan + PM_SCAN_HEAD);
+        pk_places = nullptr;
+        return true;
+    }
+
+    // The register test has hit at byte k, offset i (the header starts at bit 8 k + i).  With a record for exactly that place whose attempt the
+    // device has finished: what the attempt leaves behind -- a packet, a count of corrections, nothing -- and the rest of the byte in which it
+    // ends through the machine; returns that byte.  -1: no such record, the machine takes it from here as ever.
+    int64_t take_record(const uint8_t *d, const int64_t *a, int64_t k, int i)
+    {
+        using namespace pm_il2p;
+        Rec r{};
+        for (; pk_cursor < pk_records; ++pk_cursor) {
+            memcpy(&r, pk_places + 16 * (int64_t)pk_cursor, 16);
+            if ((int64_t)(r.at >> 3) >= k) break;
+        }
+        if (pk_cursor >= pk_records || (int64_t)(r.at >> 3) != k || (int)(r.at & 7) + 1 != i) return -1;
+        if (r.status == kIncomplete || r.status == kNotPlaced) return -1;
+        auto byte_at = [d](int64_t bit) -> unsigned {
+            const int s = (int)(bit & 7);
+            const unsigned v = d[bit >> 3];
+            return s ? ((v << s) | ((unsigned)d[(bit >> 3) + 1] >> (8 - s))) & 0xFF : v;
+        };
+        int64_t E = 8 * k + i + (r.status == kHeaderFail ? (int64_t)kHeaderBits : (int64_t)r.end);
+        if (r.status != kHeaderFail) corrected += r.corrected;
+        if (r.status == kDone) {
+            memcpy(buf, pk_area + r.off, 13);
+            header();
+            data.insert(data.end(), pk_area + r.off + 13, pk_area + r.off + 13 + r.count);
+            if (want_crc) {
+                int c = 0;
+                for (int q = 0; q < 4; ++q) c += kHamming74[byte_at(E + 8 * q) & 0x7F] << (12 - 4 * q);     // il2p.py:509-512
+                E += 32;
+                data.push_back((uint8_t)(c & 0xFF));
+                data.push_back((uint8_t)(c >> 8));
+                emit(a[(E - 1) >> 3], sink);
+            } else {
+                finish(a[(E - 1) >> 3], sink);
+            }
+        }
+        const int64_t ke = (E - 1) >> 3;
+        const int rest = (int)(8 * (ke + 1) - E);
+        state = kSync;
+        word = byte_at(E - 8);
+        sync_run = 0;
+        nbits = nbuf = 0;
+        feed_bits(((unsigned)d[ke] << (8 - rest)) & 0xFF, rest, a[ke], sink);
+        return ke;
+    }
+
     // first set bit of the candidate bitmap at or behind byte k, n if there is none (bit k & 63 of little-endian word k >> 6)
     static int64_t next_candidate(const uint8_t *cand, int64_t k, int64_t n)
     {
@@ -784,6 +756,14 @@ struct Il2p : pm_codec {
                 nbits += 8;
                 continue;
             }
+            if (pk_places) {
+                const int64_t ke = take_record(d, a, k, i);
+                if (ke >= 0) {
+                    skipped += ke - k;
+                    k = ke;
+                    continue;
+                }
+            }
             const unsigned b = ((unsigned)d[k] << i) & 0xFF;
             nbits = 0;
             state = kHeader;
@@ -813,47 +793,7 @@ struct Il2p : pm_codec {
         return table[tol].data();
     }
 
-    static void descramble(uint8_t *p, int n)
-    {   // il2p.py:160-163 + lfsr.py:54-92: x^9 + x^4 + 1 (0x211), register preset 0x1F0.  The register step is linear over GF(2), so
-        // a byte's eight steps are (what the register alone does) XOR (what the byte alone does): four small tables built from the
-        // bit-serial loop below, which is the reference's (a 100-byte block took 800 of its iterations).
-        struct Tab {
-            uint8_t out_reg[512], out_in[256];
-            uint16_t nxt_reg[512], nxt_in[256];
-            Tab()
-            {
-                auto run = [](unsigned reg, unsigned b, unsigned &regout) {
-                    unsigned w = 0;
-                    for (int i = 0; i < 8; ++i) {
-                        w = (w << 1) & 0xFE;
-                        if (b & 0x80) reg ^= 0x211;
-                        w |= reg & 1;
-                        b <<= 1;
-                        reg >>= 1;
-                    }
-                    regout = reg;
-                    return w;
-                };
-                for (unsigned r = 0; r < 512; ++r) {
-                    unsigned ro;
-                    out_reg[r] = (uint8_t)run(r, 0, ro);
-                    nxt_reg[r] = (uint16_t)ro;
-                }
-                for (unsigned b = 0; b < 256; ++b) {
-                    unsigned ro;
-                    out_in[b] = (uint8_t)run(0, b, ro);
-                    nxt_in[b] = (uint16_t)ro;
-                }
-            }
-        };
-        static const Tab t;
-        unsigned reg = 0x1F0;
-        for (int k = 0; k < n; ++k) {
-            const unsigned b = p[k];
-            p[k] = (uint8_t)(t.out_reg[reg] ^ t.out_in[b]);
-            reg = (unsigned)(t.nxt_reg[reg] ^ t.nxt_in[b]);
-        }
-    }
+    static void descramble(uint8_t *p, int n) { pm_il2p::descramble(p, n); }     // il2p.py:160-163 + lfsr.py:54-92: pm_il2p_core.h
 
     void rs(int roots)
     {
@@ -1241,6 +1181,20 @@ int pm_codec_decode_framed(pm_codec *c, const uint8_t *h_plain, const int64_t *h
     return PM_OK;
 }
 
+int pm_codec_decode_packets(pm_codec *c, const uint8_t *h_plain, const int64_t *h_addr, int64_t n, const void *h_scan, int64_t *h_pending)
+{
+    if (!c || n < 0 || (n > 0 && (!h_plain || !h_addr)) || !h_scan || !h_pending)
+        return pm_set_error(PM_ERR_ARG, "pm_codec_decode_packets: bad argument");
+    if (c->kind != 1) return pm_set_error(PM_ERR_ARG, "pm_codec_decode_packets: packets are made for IL2P codecs only");
+    if (!c->fresh) return pm_set_error(PM_ERR_ARG, "pm_codec_decode_packets: the codec has been fed before (the lists are made for a just-created decoder)");
+    if (!c->feed_packets(h_plain, h_addr, n, static_cast<const uint8_t *>(h_scan)))
+        return pm_set_error(PM_ERR_ARG, "pm_codec_decode_packets: the packet table does not belong to a stream of %lld bytes", (long long)n);
+    c->fresh = false;
+    c->fed += n;
+    *h_pending = (int64_t)c->sink.q.size();
+    return PM_OK;
+}
+
 int pm_codec_walked(pm_codec *c, int64_t *h_walked, int64_t *h_jumped)
 {
     if (!c) return pm_set_error(PM_ERR_ARG, "pm_codec_walked: no codec");
@@ -1311,8 +1265,9 @@ int pm_host_decode_batch(pm_host_job *jobs, int njobs, int threads)
             const uint8_t *bytes = scan + PM_SCAN_HEAD + PM_SCAN_LIST_BYTES(q.codec->kind, q.n);
             if (q.h_plain && q.n > 0) memcpy(q.h_plain, bytes, (size_t)q.n);
             memcpy(&q.lfsr_state, scan, 8);
-            q.status = q.scan_frames ? pm_codec_decode_framed(q.codec, bytes, addr, q.n, scan, &q.pending)
-                                     : pm_codec_decode_scanned(q.codec, bytes, addr, q.n, scan, &q.pending);
+            q.status = q.scan_frames    ? pm_codec_decode_framed(q.codec, bytes, addr, q.n, scan, &q.pending)
+                       : q.scan_packets ? pm_codec_decode_packets(q.codec, bytes, addr, q.n, scan, &q.pending)
+                                        : pm_codec_decode_scanned(q.codec, bytes, addr, q.n, scan, &q.pending);
             return;
         }
         uint8_t *out = q.h_plain ? q.h_plain : plain.data();

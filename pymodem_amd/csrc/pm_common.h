@@ -50,6 +50,8 @@ struct pm_tuning {
     int bitscan_tile_words = 0;        // PM_BITSCAN_TILE_WORDS: 64-bit words per tile of pm_stream_scan, 1 .. 256 (0: the default, 256)
     int pipe_scan = 0;                 // PM_PIPE_SCAN: a pm_pipe made on this context runs pm_stream_scan behind its slicers and decodes from its lists
     int bitscan_frame_words = 0;       // PM_BITSCAN_FRAME_WORDS: 64-bit words of a frame's span per trip of pm_stream_scan's frames launch, 1 .. 64 (0: the default, 64)
+    int bitscan_packet_waves = 0;      // PM_BITSCAN_PACKET_WAVES: waves per job of pm_stream_scan's blocks launch, 1 .. 1024 (0: the default, 64)
+    int pipe_packets = 0;              // PM_PIPE_PACKETS: pipe_scan, and the IL2P chains' attempts (headers and RS blocks) are made on the device too
     int pipe_frames = 0;               // PM_PIPE_FRAMES: pipe_scan, and the AX.25 chains' frames (de-stuffed bytes and CRC) come from the device too
     int sweep_no_tail = 0;             // PM_SWEEP_NO_TAIL: the matrix-pipe sweep sends every uncertain sample to the list (round 4), none to its own workgroup's exact chain
 };
