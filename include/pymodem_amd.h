@@ -58,6 +58,7 @@ int pm_device_cus(int device);      /* compute units of the device (0 if it cann
 /* Diagnostic switches of a context's launchers (kernel shapes kept for comparison, traces; README.md lists them).  A context reads
  * its switches from the environment (PM_<NAME>) once, when it is made; this call sets one afterwards.  No switch changes a result. */
 int pm_ctx_tune(pm_ctx *ctx, const char *name, int64_t value);
+int pm_ctx_tuned(pm_ctx *ctx, const char *name, int64_t *h_value);      /* the switch's value as the context holds it now */
 int pm_ctx_destroy(pm_ctx *ctx);
 /* Cross-stream ordering without a host wait.  pm_event_record marks the point reached by ctx's stream (creating the event when
  * *event is NULL); pm_event_wait makes everything submitted to ctx AFTER the call wait for that point.  Same device only. */
@@ -547,6 +548,24 @@ int pm_lbatch_run_sliced(pm_lbatch *batch, const int16_t *const *h_d_audio, int 
  * min(count, cap) steps (padded to 8 bytes) then its data bytes (padded to 8).  On the ctx stream; nrows <= 4096. */
 int pm_rows_gather(pm_ctx *ctx, const pm_rowslice_rec *d_recs, const uint8_t *d_data, const uint16_t *d_steps, int64_t cap, int64_t row0, int nrows,
                    void *d_block, size_t block_bytes);
+/* pm_stream_scan for rows [row0, row0 + nrows) of such a run, one call for the lot: row row0 + r is a stream of chain (row0 + r) % nchains
+ * (what pm_scan_job says about a stream apart from where it lies), its bytes the n = min(count, cap) bytes at d_data + (row0 + r) * cap.
+ * For row r, at d_block + h_offsets[r]: the row's n address steps (uint16, padded to 8 bytes, as pm_rows_gather writes them) and directly
+ * behind them exactly what pm_stream_scan writes for a job with these bytes and this chain -- PM_SCAN_HEAD, the list, the descrambled
+ * bytes, with frames or packets the table and the area.  The raw slicer bytes are not repeated.  h_counts[r]: that n as the host read it
+ * from the records, for the grids, *h_used and h_offsets; the kernels go by a row table that a first small launch makes on the device
+ * from d_recs itself (block offset, n, first tile, first places in the device-side lists; pm_bitscan_rows.h), and a row whose part would
+ * pass block_bytes or what h_counts sized is left out.  Nothing is uploaded, allocated beyond the context's scratch or waited for;
+ * d_block (8-byte aligned) may be page-locked host memory.  nrows <= 4096, nchains <= 64, n <= 2^29; PM_ERR_CAPACITY with *h_used set as in
+ * pm_stream_scan.  The tunes bitscan_tile_words, bitscan_frame_words and bitscan_packet_waves mean what they mean there (by default a row's
+ * events are shared by 16 waves and its placed records by 8); results do not depend on them. */
+typedef struct pm_rows_scan_chain {
+    uint64_t lfsr_poly, lfsr_state;
+    int32_t lfsr_invert, codec_kind, sync_tol, frames, packets, il2p_crc, il2p_disable_rs, il2p_min_dist;
+} pm_rows_scan_chain;
+int pm_rows_scan(pm_ctx *ctx, const pm_rowslice_rec *d_recs, const uint8_t *d_data, const uint16_t *d_steps, int64_t cap, int64_t row0, int nrows,
+                 const pm_rows_scan_chain *h_chains, int nchains, const int64_t *h_counts, void *d_block, size_t block_bytes, int64_t *h_offsets,
+                 size_t *h_used);
 pm_ctx *pm_lbatch_front_ctx(pm_lbatch *batch);       /* the engine's own contexts, for pm_prof_*: band-pass, AGC, Hilbert of chunk t + 1 ... */
 pm_ctx *pm_lbatch_tail_ctx(pm_lbatch *batch);        /* ... and the matched filters of chunk t - 1, beside the loops of chunk t on the caller's */
 pm_ctx *pm_lbatch_loop_ctx(pm_lbatch *batch);        /* ... or on the engine's loop context, when the loops have compute units of their own (else NULL) */
@@ -627,7 +646,7 @@ int pm_codec_walked(pm_codec *c, int64_t *h_walked, int64_t *h_jumped);
  * codec.  The first failing job's code is returned (its status field holds it too). */
 typedef struct pm_host_job {
     pm_codec *codec;
-    const uint8_t *h_data;        /* the slicer's bytes ...                       */
+    const uint8_t *h_data;        /* the slicer's bytes ... (may be NULL with h_scan: bytes and register come from the block) */
     const int64_t *h_addr;        /* ... and their stream addresses               */
     int64_t n;
     uint64_t lfsr_poly;

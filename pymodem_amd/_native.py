@@ -95,6 +95,13 @@ class ScanJob(ctypes.Structure):
                 ("packets", ctypes.c_int32), ("il2p_crc", ctypes.c_int32), ("il2p_disable_rs", ctypes.c_int32), ("il2p_min_dist", ctypes.c_int32)]
 
 
+class RowsScanChain(ctypes.Structure):
+    """pm_rows_scan_chain"""
+    _fields_ = [("lfsr_poly", ctypes.c_uint64), ("lfsr_state", ctypes.c_uint64),
+                ("lfsr_invert", ctypes.c_int32), ("codec_kind", ctypes.c_int32), ("sync_tol", ctypes.c_int32), ("frames", ctypes.c_int32),
+                ("packets", ctypes.c_int32), ("il2p_crc", ctypes.c_int32), ("il2p_disable_rs", ctypes.c_int32), ("il2p_min_dist", ctypes.c_int32)]
+
+
 SCAN_HEAD = 32        # PM_SCAN_HEAD
 
 
@@ -121,6 +128,21 @@ def scan_packet_table_bytes(n):
 def scan_packet_area_bytes(n):
     """PM_SCAN_PACKET_AREA_BYTES: the packet area, behind the table."""
     return (n + 7) // 8 * 8
+
+
+def scan_part_bytes(kind, frames, packets, n):
+    """What pm_stream_scan writes for a job of n bytes (pm_rows::scan_bytes): record, list, bytes, with frames or packets table and area."""
+    b = SCAN_HEAD + scan_list_bytes(kind, n) + (n + 7) // 8 * 8
+    if frames:
+        b += scan_frame_table_bytes(n) + scan_frame_area_bytes(n)
+    if packets:
+        b += scan_packet_table_bytes(n) + scan_packet_area_bytes(n)
+    return b
+
+
+def rows_scan_steps_bytes(n):
+    """The address steps in front of a row's scan part in a pm_rows_scan block (pm_rows::steps_bytes)."""
+    return (2 * n + 7) // 8 * 8
 
 
 def scan_packet_dtype():
@@ -231,6 +253,7 @@ _SIGS = {
     "pm_ctx_create": ([_int, ctypes.POINTER(_vp)], _int),
     "pm_ctx_create_prio": ([_int, _int, ctypes.POINTER(_vp)], _int),
     "pm_ctx_tune": ([_vp, ctypes.c_char_p, _i64], _int),
+    "pm_ctx_tuned": ([_vp, ctypes.c_char_p, ctypes.POINTER(_i64)], _int),
     "pm_d2d": ([_vp, _vp, _vp, ctypes.c_size_t], _int),
     "pm_host_pin": ([_vp, _vp, ctypes.c_size_t], _int),
     "pm_host_unpin": ([_vp], _int),
@@ -291,6 +314,8 @@ _SIGS = {
     "pm_lbatch_geometry": ([_vp, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)], _int),
     "pm_lbatch_run_sliced": ([_vp, ctypes.POINTER(_vp), _int, _i64, _vp, _int, _vp, _vp, _i64, _vp, ctypes.POINTER(_i64)], _int),
     "pm_rows_gather": ([_vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, ctypes.c_size_t], _int),
+    "pm_rows_scan": ([_vp, _vp, _vp, _vp, _i64, _i64, _int, ctypes.POINTER(RowsScanChain), _int, ctypes.POINTER(_i64), _vp, ctypes.c_size_t,
+                     ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_size_t)], _int),
     "pm_lbatch_run": ([_vp, ctypes.POINTER(_vp), _int, _i64, _vp, _vp, _i64, ctypes.POINTER(_i64)], _int),
     "pm_lbatch_front_ctx": ([_vp], _vp),
     "pm_lbatch_tail_ctx": ([_vp], _vp),

@@ -109,6 +109,46 @@ def _host_rows(chains, sliced, chain_ids=None):
     return views
 
 
+def _host_rows_scanned(chains, fetched, chain_ids=None, frames=False, packets=False):
+    """_host_rows for rows that SlicedRun.fetch_scanned brought: fetched[j] = (address steps, first address, n, the row's scan part).  The
+    LFSR has run on the device -- the descrambled bytes and the register come from the scan part (pm_host_job.h_scan, h_data = NULL) -- and the
+    codecs, which must be in their just-created state, decode from its lists: AX.25 from the frame table when `frames`, IL2P from the
+    packet table when `packets`."""
+    import ctypes
+    from ._native import HostJob, check, lib, packet_dtype, quick
+    n = len(chains)
+    jobs = (HostJob * n)()
+    for j, (ch, (steps, first, count, scan)) in enumerate(zip(chains, fetched)):
+        jobs[j].codec = ch[4]._handle()
+        if chain_ids is not None:
+            quick().pm_codec_set_source(jobs[j].codec, int(chain_ids[j]))
+        jobs[j].h_data, jobs[j].h_addr, jobs[j].n = None, None, int(count)
+        jobs[j].h_addr_delta, jobs[j].addr_first = (steps.ctypes.data if count else None), int(first)
+        jobs[j].h_scan = scan.ctypes.data
+        jobs[j].scan_frames, jobs[j].scan_packets = int(bool(frames) and ch[4]._kind == 0), int(bool(packets) and ch[4]._kind == 1)
+        jobs[j].lfsr_poly, jobs[j].lfsr_state, jobs[j].lfsr_invert = ch[3].polynomial, ch[3].shift_register, int(bool(ch[3].invert))
+    threads = _host_threads()
+    rc = lib().pm_host_decode_batch(jobs, n, threads)
+    for j, ch in enumerate(chains):             # the registers are taken back from the records
+        ch[3].shift_register = jobs[j].lfsr_state
+    check(rc)
+    counts = (ctypes.c_int64 * n)(*[jobs[j].pending for j in range(n)])
+    handles = (ctypes.c_void_p * n)(*[jobs[j].codec for j in range(n)])
+    block = np.empty(sum(counts), dtype=packet_dtype())
+    check(lib().pm_codec_fetch_batch(handles, counts, n, block.ctypes.data_as(ctypes.c_void_p), threads))
+    views, at = [], 0
+    for c in counts:
+        views.append(block[at:at + c])
+        at += c
+    return views
+
+
+def _host_stages_scanned(chains, fetched, frames=False, packets=False):
+    """_host_stages for every chain of a recording from fetch_scanned's rows: PacketMeta lists."""
+    from .packet_meta import rows_to_packets
+    return [rows_to_packets(v, ch[4].identifier) for ch, v in zip(chains, _host_rows_scanned(chains, fetched, None, frames, packets))]
+
+
 _POOL = None
 _USE_SWEEP = True          # pm_afsk_sweep_signs for gain sweeps (tests switch it off to compare against the exact group path)
 _GROUP_RUN_QUICK = [__import__("os").environ.get("PYMODEM_AMD_GROUP_RUN_QUICK", "0") != "0"]     # measured: submit 0.16 ms instead of 0.4, the step unchanged

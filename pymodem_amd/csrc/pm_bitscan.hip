@@ -16,9 +16,13 @@
 // places in the packet area and finishes what ends with the header; the blocks launch, a fixed number of waves per job, decodes the payload
 // blocks of the placed ones -- syndromes, Chien search and descrambler across the lanes, Berlekamp and Forney on one -- and writes packet
 // and record.  Both read the slicer bytes and the scratch, never the block.
+// The kernels take their jobs from a source that is a template parameter: pm_stream_scan's table of up to 64 jobs, passed by value, or
+// pm_rows_scan's row table for up to 4096 rows of a sliced engine run, which a small prepare launch makes in scratch from the rows' records
+// (pm_bitscan_rows.h).  Either hands a kernel one Job; the launches, their order and what they write for a job are the same.
 #include "pm_common.h"
 #include "pm_bitscan_events.h"
 #include "pm_bitscan_frames.h"
+#include "pm_bitscan_rows.h"
 #include "pm_il2p_core.h"
 #include <algorithm>
 #include <cstring>
@@ -29,6 +33,18 @@ using namespace pm_events;        // what decides the event list: pm_bitscan_eve
 
 constexpr int kScanJobs = 64;
 constexpr int kLanes = 256;                 // lanes of a workgroup = most words of a tile
+
+// A job as the kernels see it, whichever table it comes from: pm_stream_scan's by-value ScanJobs or pm_rows_scan's row table (RowJobs)
+struct Job {
+    const uint8_t *data;
+    uint64_t poly, reg0;
+    int64_t off;                            // the job's record in the block
+    int64_t ev0, pk0;
+    int32_t n, tile0, tile_end;
+    int kind, invert, tol;
+    int pkopt;
+    bool ok;                                // false: the job is left out, nothing is stored for it (rows only)
+};
 
 struct ScanJobs {
     const uint8_t *data[kScanJobs];
@@ -42,6 +58,54 @@ struct ScanJobs {
     int32_t frame_words;
     int32_t pk0[kScanJobs];                 // packets: the job's first place in the device-side candidate list, records and work list, -1: no packets
     uint8_t pkopt[kScanJobs];               // packets: the codec's crc | disable_rs << 1 | min_dist (0 .. 9) << 2
+
+    __device__ int tiles() const { return tile0[njobs]; }
+    __device__ int job_of_tile(int tile) const
+    {
+        int j = 0;
+        while (j + 1 < njobs && tile0[j + 1] <= tile) ++j;
+        return j;
+    }
+    __device__ Job job(int j) const
+    {
+        return Job{data[j], poly[j], reg0[j], off[j], ev0[j], pk0[j], n[j], tile0[j], tile0[j + 1], kind[j], invert[j], tol[j], pkopt[j], true};
+    }
+    __device__ void copy_steps(uint8_t *, const Job &, int, int64_t) const {}      // (the job form's block has no steps)
+};
+
+// pm_rows_scan's source: the row table that the prepare launch leaves in scratch (pm_bitscan_rows.h), the rows' bytes where
+// pm_lbatch_run_sliced left them, and the chains' parameters by value.  Row r of the call is a stream of chain (row0 + r) % nchains.
+struct RowJobs {
+    const pm_rows::Entry *table;            // nrows + 1 entries, the last one the totals
+    const uint8_t *data;
+    const uint16_t *steps;
+    int64_t cap, row0;
+    uint64_t poly[pm_rows::kMaxChains], reg0[pm_rows::kMaxChains];
+    int8_t kind[pm_rows::kMaxChains], invert[pm_rows::kMaxChains], tol[pm_rows::kMaxChains], frames[pm_rows::kMaxChains], packets[pm_rows::kMaxChains];
+    uint8_t pkopt[pm_rows::kMaxChains];
+    int32_t nrows, nchains, tile_words, frame_words;
+
+    __device__ int tiles() const { return table[nrows].tile0; }
+    __device__ int job_of_tile(int tile) const
+    {
+        const pm_rows::Entry *t = table;
+        return pm_rows::row_of_tile([t](int i) { return t[i].tile0; }, nrows, tile);
+    }
+    __device__ Job job(int j) const
+    {
+        const pm_rows::Entry e = table[j];
+        const int c = (int)((row0 + j) % nchains);
+        return Job{data + (row0 + j) * cap, poly[c], reg0[c], e.off + pm_rows::steps_bytes(e.n), e.ev0, e.pk0, e.n, e.tile0, table[j + 1].tile0,
+                   kind[c], invert[c], tol[c], pkopt[c], e.off >= 0};
+    }
+    // the row's address steps in front of its scan part, as pm_rows_gather writes them: the lane of data word w takes step words 2 w and 2 w + 1
+    __device__ void copy_steps(uint8_t *block, const Job &jb, int j, int64_t w) const
+    {
+        const int64_t sw = pm_rows::steps_bytes(jb.n) >> 3;
+        const uint64_t *src = reinterpret_cast<const uint64_t *>(steps + (row0 + j) * cap);      // cap is a multiple of 8: rows are aligned
+        uint64_t *dst = reinterpret_cast<uint64_t *>(block + jb.off) - sw;
+        for (int64_t i = 2 * w; i < 2 * w + 2 && i < sw; ++i) dst[i] = src[i];
+    }
 };
 struct PkRec {                              // the headers launch's copy of a record for the blocks launch, with the 13 descrambled header bytes
     pm_il2p::Rec r;
@@ -49,6 +113,8 @@ struct PkRec {                              // the headers launch's copy of a re
 };
 constexpr int kFrameWaves = 256;            // waves that share a job's events in the frames launch (a wave a workgroup: the others leave at once)
 constexpr int kPacketWaves = 64;            // waves that share a job's placed records in the blocks launch
+constexpr int kRowFrameWaves = 16;          // the same for a row of pm_rows_scan: thousands of rows of tens to hundreds of KB each
+constexpr int kRowPacketWaves = 8;
 constexpr uint32_t kClosesNothing = 0xFFFFFFFEu;   // F of the stream's first flag in the device-side copy when no frame ends there
 
 __device__ inline uint64_t load_word(const uint8_t *d, int64_t n, int64_t w)
@@ -64,30 +130,30 @@ __device__ inline uint64_t load_word(const uint8_t *d, int64_t n, int64_t w)
     return __brevll(__builtin_bswap64(v));
 }
 
-__device__ inline uint64_t plain_word(const ScanJobs &J, int j, int64_t w, uint64_t cur, uint64_t prev)
+__device__ inline uint64_t plain_word(const Job &jb, int64_t w, uint64_t cur, uint64_t prev)
 {
     // the LFSR's output word from input word w and the one before it
     uint64_t o = 0;
-    for (uint64_t p = J.poly[j]; p; p &= p - 1) {
+    for (uint64_t p = jb.poly; p; p &= p - 1) {
         const int k = __builtin_ctzll(p);
         o ^= k ? (cur << k) | (prev >> (64 - k)) : cur;
     }
-    if (w == 0) o ^= J.reg0[j];             // bit t of the incoming register meets stream bit t
-    return J.invert[j] ? ~o : o;
+    if (w == 0) o ^= jb.reg0;             // bit t of the incoming register meets stream bit t
+    return jb.invert ? ~o : o;
 }
 
 // the descrambled stream's word w (zeros outside the stream), and 64 / 32 of its bits from any bit B on, the first in bit 0
-__device__ inline uint64_t stream_word(const ScanJobs &J, int j, int64_t n, int64_t w)
+__device__ inline uint64_t stream_word(const Job &jb, int64_t n, int64_t w)
 {
     if (w < 0 || 8 * w >= n) return 0;
-    return plain_word(J, j, w, load_word(J.data[j], n, w), load_word(J.data[j], n, w - 1));
+    return plain_word(jb, w, load_word(jb.data, n, w), load_word(jb.data, n, w - 1));
 }
-__device__ inline uint64_t stream_bits64(const ScanJobs &J, int j, int64_t n, int64_t B)
+__device__ inline uint64_t stream_bits64(const Job &jb, int64_t n, int64_t B)
 {
     const int64_t w = B >> 6;
     const int s = (int)(B & 63);
-    const uint64_t lo = stream_word(J, j, n, w);
-    return s ? (lo >> s) | (stream_word(J, j, n, w + 1) << (64 - s)) : lo;
+    const uint64_t lo = stream_word(jb, n, w);
+    return s ? (lo >> s) | (stream_word(jb, n, w + 1) << (64 - s)) : lo;
 }
 __device__ inline unsigned stream_byte(uint64_t bits, int q) { return __brev((unsigned)(bits >> (8 * q)) & 0xFFu) >> 24; }     // byte q of them, its first bit on top
 
@@ -154,34 +220,33 @@ struct TileSumLds {
     __device__ void last_flag(int32_t P) { atomicMax(&ts->last_flag, P); }
 };
 
-__device__ inline int job_of_tile(const ScanJobs &J, int tile)
-{
-    int j = 0;
-    while (j + 1 < J.njobs && J.tile0[j + 1] <= tile) ++j;
-    return j;
-}
-
 __host__ __device__ inline int64_t list_bytes(int kind, int64_t n) { return PM_SCAN_LIST_BYTES(kind, n); }
 
 // Launch 1: per tile the descrambled bytes, the IL2P bitmap, the tile's summary.
-__global__ __launch_bounds__(kLanes) void bitscan_tile_kernel(ScanJobs J, uint8_t *block, TileSum *sums)
+template <class Jobs>
+__global__ __launch_bounds__(kLanes) void bitscan_tile_kernel(Jobs J, uint8_t *block, TileSum *sums)
 {
     __shared__ Seg lds[kLanes];
     __shared__ TileSum ts;
-    const int tile = blockIdx.x, j = job_of_tile(J, tile), tw = J.tile_words;
-    const int64_t n = J.n[j], nw = (n + 7) / 8;
-    const int64_t w = (int64_t)(tile - J.tile0[j]) * tw + threadIdx.x;
+    const int tile = blockIdx.x, tw = J.tile_words;
+    if (tile >= J.tiles()) return;
+    const int j = J.job_of_tile(tile);
+    const Job jb = J.job(j);
+    if (!jb.ok) return;
+    const int64_t n = jb.n, nw = (n + 7) / 8;
+    const int64_t w = (int64_t)(tile - jb.tile0) * tw + threadIdx.x;
     const bool active = (int)threadIdx.x < tw && w < nw;
-    const int kind = J.kind[j];
-    const uint8_t *d = J.data[j];
-    uint8_t *base = block + J.off[j], *list = base + PM_SCAN_HEAD, *plain = list + list_bytes(kind, n);
+    const int kind = jb.kind;
+    const uint8_t *d = jb.data;
+    uint8_t *base = block + jb.off, *list = base + PM_SCAN_HEAD, *plain = list + list_bytes(kind, n);
     uint64_t x = 0, xp = 0, valid = 0;
     if (active) {
         const uint64_t i0 = load_word(d, n, w), i1 = load_word(d, n, w - 1), i2 = load_word(d, n, w - 2);
         valid = valid_bits(n, w);
-        x = plain_word(J, j, w, i0, i1) & valid;
-        xp = w ? plain_word(J, j, w - 1, i1, i2) : 0;           // (a fresh decoder: zeros in front of the stream)
+        x = plain_word(jb, w, i0, i1) & valid;
+        xp = w ? plain_word(jb, w - 1, i1, i2) : 0;           // (a fresh decoder: zeros in front of the stream)
         *reinterpret_cast<uint64_t *>(plain + 8 * w) = __builtin_bswap64(__brevll(x));       // the bytes are padded to 8: the last store is whole
+        J.copy_steps(block, jb, j, w);
     }
     if (threadIdx.x == 0) {
         ts = tile_sum_empty();
@@ -192,7 +257,7 @@ __global__ __launch_bounds__(kLanes) void bitscan_tile_kernel(ScanJobs J, uint8_
         // il2p.py:367-376 at the eight bit offsets of every byte k >= 4: the 32 bits in front of each against both patterns
         if (active) {
             const uint64_t C = __brevll(x), P = __brevll(xp);   // most significant bit first: byte 0 on top
-            const int tol = J.tol[j];
+            const int tol = jb.tol;
             unsigned bits = 0;
             for (int b = 0; b < 8; ++b) {
                 const int64_t k = 8 * w + b;
@@ -222,11 +287,14 @@ __global__ __launch_bounds__(kLanes) void bitscan_tile_kernel(ScanJobs J, uint8_
 }
 
 // Launch 2: a wave per stream takes the summaries in order, 64 at a time (a lane loads one, all lanes step through them together).
-__global__ __launch_bounds__(64) void bitscan_combine_kernel(ScanJobs J, uint8_t *block, const TileSum *sums, TileCarry *carries, int32_t *counts)
+template <class Jobs>
+__global__ __launch_bounds__(64) void bitscan_combine_kernel(Jobs J, uint8_t *block, const TileSum *sums, TileCarry *carries, int32_t *counts)
 {
     const int j = blockIdx.x, lane = threadIdx.x, tw = J.tile_words;
-    const int t0 = J.tile0[j], nt = J.tile0[j + 1] - t0;
-    const int kind = J.kind[j];
+    const Job jb = J.job(j);
+    if (!jb.ok) return;
+    const int t0 = jb.tile0, nt = jb.tile_end - t0;
+    const int kind = jb.kind;
     Combine st = combine_start();
     int32_t cands = 0;
     for (int r0 = 0; r0 < nt; r0 += 64) {
@@ -245,11 +313,11 @@ __global__ __launch_bounds__(64) void bitscan_combine_kernel(ScanJobs J, uint8_t
     }
     if (lane == 0) {
         // the register as the stream leaves it (lfsr.py:30-51): what is left of the incoming one, and the taps of the last 63 input bits
-        const int64_t n = J.n[j], T = 8 * n;
-        uint64_t reg = T < 64 ? J.reg0[j] >> T : 0;
+        const int64_t n = jb.n, T = 8 * n;
+        uint64_t reg = T < 64 ? jb.reg0 >> T : 0;
         for (int64_t t = T > 63 ? T - 63 : 0; t < T; ++t)
-            if ((J.data[j][t >> 3] >> (7 - (t & 7))) & 1) reg ^= J.poly[j] >> (T - t);
-        uint8_t *rec = block + J.off[j];
+            if ((jb.data[t >> 3] >> (7 - (t & 7))) & 1) reg ^= jb.poly >> (T - t);
+        uint8_t *rec = block + jb.off;
         *reinterpret_cast<uint64_t *>(rec) = reg;
         const Record r = combine_record(st);
         *reinterpret_cast<int64_t *>(rec + 8) = r.bail_bit;
@@ -262,22 +330,26 @@ __global__ __launch_bounds__(64) void bitscan_combine_kernel(ScanJobs J, uint8_t
 
 // Launch 3: the events of every AX.25 tile, at the places the combine counted out; packets: the candidates {k, S} of every IL2P tile likewise,
 // into the device-side list.
-__global__ __launch_bounds__(kLanes) void bitscan_emit_kernel(ScanJobs J, uint8_t *block, const TileCarry *carries, uint2 *copies, uint32_t *cands)
+template <class Jobs>
+__global__ __launch_bounds__(kLanes) void bitscan_emit_kernel(Jobs J, uint8_t *block, const TileCarry *carries, uint2 *copies, uint32_t *cands)
 {
     __shared__ Seg lds[kLanes];
     __shared__ int32_t cnt[kLanes];
-    const int tile = blockIdx.x, j = job_of_tile(J, tile), tw = J.tile_words;
-    if (J.kind[j] == 1 && J.pk0[j] >= 0) {
-        const int64_t n = J.n[j], nw = (n + 7) / 8, w = (int64_t)(tile - J.tile0[j]) * tw + threadIdx.x, places = n / 64 + 2;
+    const int tile = blockIdx.x, tw = J.tile_words;
+    if (tile >= J.tiles()) return;
+    const Job jb = J.job(J.job_of_tile(tile));
+    if (!jb.ok) return;
+    if (jb.kind == 1 && jb.pk0 >= 0) {
+        const int64_t n = jb.n, nw = (n + 7) / 8, w = (int64_t)(tile - jb.tile0) * tw + threadIdx.x, places = n / 64 + 2;
         unsigned bits = 0, offs = 0;                        // the word's candidate bytes, and the smallest offset that hits in each (3 bits a byte)
         if ((int)threadIdx.x < tw && w < nw) {
-            const uint8_t *d = J.data[j];
+            const uint8_t *d = jb.data;
             const uint64_t i0 = load_word(d, n, w), i1 = load_word(d, n, w - 1), i2 = load_word(d, n, w - 2);
-            const uint64_t C = __brevll(plain_word(J, j, w, i0, i1) & valid_bits(n, w)), P = __brevll(w ? plain_word(J, j, w - 1, i1, i2) : 0);
+            const uint64_t C = __brevll(plain_word(jb, w, i0, i1) & valid_bits(n, w)), P = __brevll(w ? plain_word(jb, w - 1, i1, i2) : 0);
             for (int b = 0; b < 8; ++b) {
                 const int64_t k = 8 * w + b;
                 if (k < 4 || k >= n) continue;
-                const unsigned hits = il2p_byte_hits(C, P, b, J.tol[j]);
+                const unsigned hits = il2p_byte_hits(C, P, b, jb.tol);
                 if (hits) {
                     bits |= 1u << b;
                     offs |= (unsigned)__builtin_ctz(hits) << (3 * b);
@@ -288,23 +360,23 @@ __global__ __launch_bounds__(kLanes) void bitscan_emit_kernel(ScanJobs J, uint8_
         int64_t at = (int64_t)carries[tile].events + (threadIdx.x ? cnt[threadIdx.x - 1] : 0);
         for (unsigned m = bits; m; m &= m - 1, ++at) {
             const int b = __builtin_ctz(m);
-            if (at < places) cands[J.pk0[j] + at] = (uint32_t)((8 * w + b) << 3) | ((offs >> (3 * b)) & 7u);
+            if (at < places) cands[jb.pk0 + at] = (uint32_t)((8 * w + b) << 3) | ((offs >> (3 * b)) & 7u);
         }
         return;
     }
-    if (J.kind[j] != 0) return;
+    if (jb.kind != 0) return;
     const TileCarry c = carries[tile];
     if (c.events < 0) return;
-    const int64_t n = J.n[j], nw = (n + 7) / 8;
-    const int64_t tbase = (int64_t)(tile - J.tile0[j]) * tw, w = tbase + threadIdx.x, B = tbase * 64;
+    const int64_t n = jb.n, nw = (n + 7) / 8;
+    const int64_t tbase = (int64_t)(tile - jb.tile0) * tw, w = tbase + threadIdx.x, B = tbase * 64;
     const bool active = (int)threadIdx.x < tw && w < nw;
     uint64_t x = 0, xp = 0, valid = 0;
     if (active) {
-        const uint8_t *d = J.data[j];
+        const uint8_t *d = jb.data;
         const uint64_t i0 = load_word(d, n, w), i1 = load_word(d, n, w - 1), i2 = load_word(d, n, w - 2);
         valid = valid_bits(n, w);
-        x = plain_word(J, j, w, i0, i1) & valid;
-        xp = w ? plain_word(J, j, w - 1, i1, i2) : 0;
+        x = plain_word(jb, w, i0, i1) & valid;
+        xp = w ? plain_word(jb, w - 1, i1, i2) : 0;
     }
     Seg total;
     const LaneIn in = lane_prepare(ax25_marks(x, xp, valid), active, lds, &total);
@@ -314,12 +386,12 @@ __global__ __launch_bounds__(kLanes) void bitscan_emit_kernel(ScanJobs J, uint8_
     const int nfound = listed_count(l);
     block_scan((int32_t)nfound, cnt, [](int32_t a, int32_t b) { return a + b; });
     const int64_t at = (int64_t)c.events + (threadIdx.x ? cnt[threadIdx.x - 1] : 0), cap = n / 19 + 2;
-    uint2 *events = reinterpret_cast<uint2 *>(block + J.off[j] + PM_SCAN_HEAD);
+    uint2 *events = reinterpret_cast<uint2 *>(block + jb.off + PM_SCAN_HEAD);
     for (int k = 0; k < nfound; ++k)
         if (at + k < cap) events[at + k] = make_uint2(listed_P(l, k), listed_F(l, k));
-    if (J.ev0[j] >= 0)
+    if (jb.ev0 >= 0)
         for (int k = 0; k < nfound; ++k)
-            if (at + k < cap) copies[J.ev0[j] + at + k] = make_uint2(listed_P(l, k), (l.nothing >> k) & 1 ? kClosesNothing : listed_F(l, k));
+            if (at + k < cap) copies[jb.ev0 + at + k] = make_uint2(listed_P(l, k), (l.nothing >> k) & 1 ? kClosesNothing : listed_F(l, k));
 }
 
 // Launch 4 (pm_scan_job.frames): a wave per listed flag {P, F} -- the events e, e + waves, ... of its job, the count read from the combine
@@ -329,15 +401,17 @@ __global__ __launch_bounds__(kLanes) void bitscan_emit_kernel(ScanJobs J, uint8_
 // line's whole bytes out to the frame area, the CRC continued over them, a lane a piece.  The line is laid out so that its 8-byte words are
 // the area's: whole words go out as one store, the bytes at a frame's two ends one by one (the neighbouring frames' bytes share those
 // words).  Up to seven bits of a byte that the trip leaves unfinished stay in the line for the next trip.
-__global__ __launch_bounds__(64) void bitscan_frames_kernel(ScanJobs J, uint8_t *block, const uint2 *copies, const int32_t *counts)
+template <class Jobs>
+__global__ __launch_bounds__(64) void bitscan_frames_kernel(Jobs J, uint8_t *block, const uint2 *copies, const int32_t *counts)
 {
     using namespace pm_frames;
     constexpr int kLineWords = 136;                         // 7 bytes of alignment, 7 bits left over, 64 words of 64 bits, and the OR's reach
     __shared__ uint32_t line[kLineWords];
     __shared__ uint16_t crc_table[256];
     const int j = blockIdx.y, lane = threadIdx.x;
-    if (J.ev0[j] < 0) return;
-    const int64_t n = J.n[j], cap = n / 19 + 2;
+    const Job jb = J.job(j);
+    if (!jb.ok || jb.ev0 < 0) return;
+    const int64_t n = jb.n, cap = n / 19 + 2;
     const int32_t count = (int32_t)(counts[j] < cap ? counts[j] : cap);
     if ((int)blockIdx.x >= count) return;
     for (int v = lane; v < 256; v += 64) {
@@ -345,12 +419,12 @@ __global__ __launch_bounds__(64) void bitscan_frames_kernel(ScanJobs J, uint8_t 
         for (int i = 0; i < 8; ++i) c = (c & 1) ? (c >> 1) ^ 0x8408u : c >> 1;      // crc_functions.py:44-55, eight bits at a time
         crc_table[v] = (uint16_t)c;
     }
-    const uint8_t *d = J.data[j];
-    uint8_t *table = block + J.off[j] + PM_SCAN_HEAD + list_bytes(0, n) + ((n + 7) & ~int64_t(7)), *area = table + PM_SCAN_FRAME_TABLE_BYTES(n);
+    const uint8_t *d = jb.data;
+    uint8_t *table = block + jb.off + PM_SCAN_HEAD + list_bytes(0, n) + ((n + 7) & ~int64_t(7)), *area = table + PM_SCAN_FRAME_TABLE_BYTES(n);
     const int fw = J.frame_words;
     auto or_word = [&](int at, uint32_t v) { atomicOr(&line[at], v); };
     for (int32_t e = (int32_t)blockIdx.x; e < count; e += (int32_t)gridDim.x) {
-        const uint2 pf = copies[J.ev0[j] + e];
+        const uint2 pf = copies[jb.ev0 + e];
         const int64_t P = pf.x, s = pf.y >= kClosesNothing ? 0 : (int64_t)pf.y;
         if (pf.y == kClosesNothing || P >= 8 * n || s >= P) {
             if (lane == 0) *reinterpret_cast<uint2 *>(table + 8 * (int64_t)e) = make_uint2(0u, 0u);
@@ -368,8 +442,8 @@ __global__ __launch_bounds__(64) void bitscan_frames_kernel(ScanJobs J, uint8_t 
             WordMarks k{0, 0};
             if (active) {
                 const uint64_t i0 = load_word(d, n, w), i1 = load_word(d, n, w - 1), i2 = load_word(d, n, w - 2);
-                x = plain_word(J, j, w, i0, i1);
-                const uint64_t xp = w ? plain_word(J, j, w - 1, i1, i2) : 0;
+                x = plain_word(jb, w, i0, i1);
+                const uint64_t xp = w ? plain_word(jb, w - 1, i1, i2) : 0;
                 const uint64_t span = low_mask(w == w_last ? (int)((P - 1) & 63) + 1 : 64) & ~low_mask(w == w_first ? (int)(s & 63) : 0);
                 k = word_marks(x, xp, span);
             }
@@ -455,20 +529,22 @@ __global__ __launch_bounds__(64) void bitscan_frames_kernel(ScanJobs J, uint8_t 
 // every passed and complete header its place in the area in candidate order; from the first that does not fit on, none is placed.  What ends
 // here -- INCOMPLETE, HEADER_FAIL, NOT_PLACED, DONE without payload -- goes to the table at once; every record is copied to scratch, and the
 // placed ones with payload are listed there for the blocks launch.
-__global__ __launch_bounds__(64) void bitscan_headers_kernel(ScanJobs J, uint8_t *block, const int32_t *counts, const uint32_t *cands, PkRec *recs, int32_t *work,
+template <class Jobs>
+__global__ __launch_bounds__(64) void bitscan_headers_kernel(Jobs J, uint8_t *block, const int32_t *counts, const uint32_t *cands, PkRec *recs, int32_t *work,
                                                              int32_t *pkcounts)
 {
     using namespace pm_il2p;
     using pm_frames::low_mask;
     __shared__ GF256 g;
     const int j = blockIdx.x, lane = threadIdx.x;
-    if (J.pk0[j] < 0) return;
+    const Job jb = J.job(j);
+    if (!jb.ok || jb.pk0 < 0) return;
     if (lane == 0) gf_build(&g);
     __syncthreads();
-    const int64_t n = J.n[j], places = n / 64 + 2, area_bytes = PM_SCAN_PACKET_AREA_BYTES(n);
-    const int32_t records = (int32_t)(counts[j] < places ? counts[j] : places), base = J.pk0[j];
-    uint8_t *table = block + J.off[j] + PM_SCAN_HEAD + list_bytes(1, n) + ((n + 7) & ~int64_t(7)), *area = table + PM_SCAN_PACKET_TABLE_BYTES(n);
-    const Opts o{J.pkopt[j] & 1, (J.pkopt[j] >> 1) & 1, J.pkopt[j] >> 2};
+    const int64_t n = jb.n, places = n / 64 + 2, area_bytes = PM_SCAN_PACKET_AREA_BYTES(n);
+    const int32_t records = (int32_t)(counts[j] < places ? counts[j] : places), base = jb.pk0;
+    uint8_t *table = block + jb.off + PM_SCAN_HEAD + list_bytes(1, n) + ((n + 7) & ~int64_t(7)), *area = table + PM_SCAN_PACKET_TABLE_BYTES(n);
+    const Opts o{jb.pkopt & 1, (jb.pkopt >> 1) & 1, jb.pkopt >> 2};
     int64_t used = 0;                                       // bytes of the area counted out so far
     int32_t nwork = 0, nplaced = 0;
     bool full = false;
@@ -484,7 +560,7 @@ __global__ __launch_bounds__(64) void bitscan_headers_kernel(ScanJobs J, uint8_t
             const int64_t H = rec_H(at);
             pr.r = rec_incomplete(at);
             if (H + kHeaderBits <= 8 * n) {
-                const uint64_t b0 = stream_bits64(J, j, n, H), b1 = stream_bits64(J, j, n, H + 64);
+                const uint64_t b0 = stream_bits64(jb, n, H), b1 = stream_bits64(jb, n, H + 64);
                 for (int q = 0; q < 8; ++q) pr.hdr[q] = (uint8_t)stream_byte(b0, q);
                 for (int q = 0; q < 7; ++q) pr.hdr[8 + q] = (uint8_t)stream_byte(b1, q);
                 pr.r = header_attempt(&g, at, pr.hdr, o, 8 * n);
@@ -538,7 +614,8 @@ __global__ __launch_bounds__(64) void bitscan_headers_kernel(ScanJobs J, uint8_t
 // XORed over the wave; if any is set, Berlekamp on lane 0, the Chien search a position per lane, Forney on lane 0, and the syndromes again;
 // the descrambler a byte per lane into the packet, which is put together in LDS behind its 13 header bytes and goes out in whole words once
 // every block has passed.  The wave writes the record whole at the end.
-__global__ __launch_bounds__(64) void bitscan_blocks_kernel(ScanJobs J, uint8_t *block, const PkRec *recs, const int32_t *work, const int32_t *pkcounts)
+template <class Jobs>
+__global__ __launch_bounds__(64) void bitscan_blocks_kernel(Jobs J, uint8_t *block, const PkRec *recs, const int32_t *work, const int32_t *pkcounts)
 {
     using namespace pm_il2p;
     using pm_frames::low_mask;
@@ -546,14 +623,15 @@ __global__ __launch_bounds__(64) void bitscan_blocks_kernel(ScanJobs J, uint8_t 
     __shared__ uint32_t buf32[64], pkt32[264];              // a block of up to 255 bytes; the packet: 13 + 1023 bytes, padded to 8
     __shared__ int syn[16], loc[17], where[17];
     const int j = blockIdx.y, lane = threadIdx.x;
-    if (J.pk0[j] < 0) return;
+    const Job jb = J.job(j);
+    if (!jb.ok || jb.pk0 < 0) return;
     if (lane == 0) gf_build(&g);
     __syncthreads();
-    const int64_t n = J.n[j];
-    const int32_t nwork = pkcounts[2 * j + 1], base = J.pk0[j];
-    uint8_t *table = block + J.off[j] + PM_SCAN_HEAD + list_bytes(1, n) + ((n + 7) & ~int64_t(7)), *area = table + PM_SCAN_PACKET_TABLE_BYTES(n);
-    const bool disable_rs = (J.pkopt[j] >> 1) & 1;
-    const int min_dist = J.pkopt[j] >> 2;
+    const int64_t n = jb.n;
+    const int32_t nwork = pkcounts[2 * j + 1], base = jb.pk0;
+    uint8_t *table = block + jb.off + PM_SCAN_HEAD + list_bytes(1, n) + ((n + 7) & ~int64_t(7)), *area = table + PM_SCAN_PACKET_TABLE_BYTES(n);
+    const bool disable_rs = (jb.pkopt >> 1) & 1;
+    const int min_dist = jb.pkopt >> 2;
     uint8_t *buf = reinterpret_cast<uint8_t *>(buf32), *pkt = reinterpret_cast<uint8_t *>(pkt32);
     // the wave's syndromes of the nb bytes in buf, four to a word, the same in every lane
     auto syndromes = [&](int nb, uint32_t *s4) {
@@ -587,7 +665,7 @@ __global__ __launch_bounds__(64) void bitscan_blocks_kernel(ScanJobs J, uint8_t 
             const int bs = block_bytes(split, b), nb = bs + 16;
             __syncthreads();
             {
-                const uint32_t v = 4 * lane < nb ? (uint32_t)stream_bits64(J, j, n, rec_H(pr.r.at) + end + 32 * lane) : 0u;
+                const uint32_t v = 4 * lane < nb ? (uint32_t)stream_bits64(jb, n, rec_H(pr.r.at) + end + 32 * lane) : 0u;
                 buf32[lane] = stream_byte(v, 0) | stream_byte(v, 1) << 8 | stream_byte(v, 2) << 16 | stream_byte(v, 3) << 24;
             }
             __syncthreads();
@@ -630,6 +708,80 @@ __global__ __launch_bounds__(64) void bitscan_blocks_kernel(ScanJobs J, uint8_t 
             place[0] = make_uint2(pr.r.at, pr.r.off);
             place[1] = make_uint2((uint32_t)count | (uint32_t)(fail ? kBlockFail : kDone) << 16 | (uint32_t)corrected << 24, end);
         }
+    }
+}
+
+// The prepare launch of pm_rows_scan: the row table from the records' counts and the chains' kinds (pm_bitscan_rows.h) -- one workgroup,
+// trips of 256 rows, a lane a row: an inclusive scan of the rows' four sums over the lanes, the carry from trip to trip.
+__global__ __launch_bounds__(kLanes) void rows_prepare_kernel(RowJobs J, const pm_rowslice_rec *recs, pm_rows::Entry *table, pm_rows::Sums limit)
+{
+    using namespace pm_rows;
+    static_assert(kTrip == kLanes, "a lane a row");
+    __shared__ Sums lds[kLanes];
+    Sums carry = sums_zero();
+    for (int r0 = 0; r0 < J.nrows; r0 += kTrip) {
+        const int r = r0 + (int)threadIdx.x, c = (int)((J.row0 + r) % J.nchains);
+        const bool active = r < J.nrows;
+        const int64_t n = active ? row_bytes(recs[J.row0 + r].count, J.cap) : 0;
+        const Sums mine = active ? row_sums(J.kind[c], J.frames[c], J.packets[c], n < kMaxBytes ? n : kMaxBytes, J.tile_words) : sums_zero();
+        const Sums upto = block_scan(mine, lds, [](const Sums &a, const Sums &b) { return sums_add(a, b); });
+        const Sums before = sums_add(carry, threadIdx.x ? lds[threadIdx.x - 1] : sums_zero());
+        carry = sums_add(carry, lds[kLanes - 1]);
+        (void)upto;
+        if (active) table[r] = row_entry(before, J.kind[c], J.frames[c], J.packets[c], n, J.tile_words, limit);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) table[J.nrows] = total_entry(carry, limit);
+}
+
+// what the launches share in context scratch, cut for `jobs` jobs (or rows)
+struct ScanScratch {
+    TileSum *sums;
+    TileCarry *carries;
+    int32_t *counts;
+    uint2 *lists;
+    uint32_t *cands;
+    int32_t *work, *pkcounts;
+    PkRec *recs;
+    uint8_t *extra;                         // `extra_bytes` behind everything, 64-byte aligned (the row table)
+};
+int scan_scratch(pm_ctx *ctx, size_t jobs, int64_t tiles, int64_t copies, int64_t places, size_t extra_bytes, ScanScratch *out)
+{
+    const size_t sums_bytes = ((size_t)tiles * sizeof(TileSum) + 63) & ~(size_t)63;
+    // (frames: the event counts and a copy of the lists stay on the device for the frames launch, behind the carries)
+    const size_t carries_bytes = ((size_t)tiles * sizeof(TileCarry) + 63) & ~(size_t)63, counts_bytes = copies || places ? jobs * sizeof(int32_t) : 0;
+    // (packets: the candidates, a copy of every record with its header bytes, the list of those with blocks to decode, and the two counts per job)
+    const size_t lists_bytes = (size_t)copies * sizeof(uint2), cands_bytes = ((size_t)places * sizeof(uint32_t) + 63) & ~(size_t)63, recs_bytes = (size_t)places * sizeof(PkRec);
+    const size_t pk_bytes = places ? 2 * cands_bytes + recs_bytes + 2 * jobs * sizeof(int32_t) : 0;
+    if (int rc = pm_scratch_reserve(ctx, sums_bytes + carries_bytes + counts_bytes + lists_bytes + pk_bytes + extra_bytes + 256)) return rc;
+    uint8_t *base = static_cast<uint8_t *>(ctx->d_scratch);
+    out->sums = reinterpret_cast<TileSum *>(base);
+    out->carries = reinterpret_cast<TileCarry *>(base + sums_bytes);
+    out->counts = copies || places ? reinterpret_cast<int32_t *>(base + sums_bytes + carries_bytes) : nullptr;
+    out->lists = reinterpret_cast<uint2 *>(base + sums_bytes + carries_bytes + counts_bytes);
+    uint8_t *pk = reinterpret_cast<uint8_t *>(((uintptr_t)out->lists + lists_bytes + 63) & ~(uintptr_t)63);
+    out->cands = reinterpret_cast<uint32_t *>(pk);
+    out->work = reinterpret_cast<int32_t *>(pk + cands_bytes);
+    out->pkcounts = reinterpret_cast<int32_t *>(pk + 2 * cands_bytes);
+    out->recs = reinterpret_cast<PkRec *>(pk + 2 * cands_bytes + 2 * jobs * sizeof(int32_t));
+    out->extra = reinterpret_cast<uint8_t *>(((uintptr_t)pk + pk_bytes + 63) & ~(uintptr_t)63);
+    return PM_OK;
+}
+
+// the launches behind either table: `emit`: some job has a list to write; frame_waves, packet_waves: the waves that share a job
+template <class Jobs>
+void scan_launch(pm_ctx *ctx, const Jobs &J, int njobs, int64_t tiles, int64_t copies, int64_t places, bool emit, uint8_t *block, const ScanScratch &s,
+                 int frame_waves, int packet_waves)
+{
+    if (tiles) hipLaunchKernelGGL(bitscan_tile_kernel<Jobs>, dim3((unsigned)tiles), dim3(kLanes), 0, ctx->stream, J, block, s.sums);
+    hipLaunchKernelGGL(bitscan_combine_kernel<Jobs>, dim3(njobs), dim3(64), 0, ctx->stream, J, block, s.sums, s.carries, s.counts);
+    if (emit && tiles) hipLaunchKernelGGL(bitscan_emit_kernel<Jobs>, dim3((unsigned)tiles), dim3(kLanes), 0, ctx->stream, J, block, s.carries, s.lists, s.cands);
+    if (copies) hipLaunchKernelGGL(bitscan_frames_kernel<Jobs>, dim3(frame_waves, njobs), dim3(64), 0, ctx->stream, J, block, s.lists, s.counts);
+    if (places) {
+        const int ptune = ctx->tune.bitscan_packet_waves;
+        hipLaunchKernelGGL(bitscan_headers_kernel<Jobs>, dim3(njobs), dim3(64), 0, ctx->stream, J, block, s.counts, s.cands, s.recs, s.work, s.pkcounts);
+        hipLaunchKernelGGL(bitscan_blocks_kernel<Jobs>, dim3(ptune > 0 ? std::min(ptune, 1024) : packet_waves, njobs), dim3(64), 0, ctx->stream, J, block, s.recs,
+                           s.work, s.pkcounts);
     }
 }
 
@@ -684,33 +836,71 @@ extern "C" int pm_stream_scan(pm_ctx *ctx, const pm_scan_job *h_jobs, int njobs,
     J.tile0[njobs] = (int32_t)tiles;
     *h_used = at;
     if (at > block_bytes) return pm_set_error(PM_ERR_CAPACITY, "pm_stream_scan: the block holds %zu bytes, the batch needs %zu", block_bytes, at);
-    const size_t sums_bytes = ((size_t)tiles * sizeof(TileSum) + 63) & ~(size_t)63;
-    // (frames: the event counts and a copy of the lists stay on the device for the frames launch, behind the carries)
-    const size_t carries_bytes = ((size_t)tiles * sizeof(TileCarry) + 63) & ~(size_t)63, counts_bytes = copies || places ? kScanJobs * sizeof(int32_t) : 0;
-    // (packets: the candidates, a copy of every record with its header bytes, the list of those with blocks to decode, and the two counts per job)
-    const size_t lists_bytes = (size_t)copies * sizeof(uint2), cands_bytes = ((size_t)places * sizeof(uint32_t) + 63) & ~(size_t)63, recs_bytes = (size_t)places * sizeof(PkRec);
-    const size_t pk_bytes = places ? 2 * cands_bytes + recs_bytes + 2 * kScanJobs * sizeof(int32_t) : 0;
-    if (int rc = pm_scratch_reserve(ctx, sums_bytes + carries_bytes + counts_bytes + lists_bytes + pk_bytes + 128)) return rc;
-    TileSum *sums = static_cast<TileSum *>(ctx->d_scratch);
-    TileCarry *carries = reinterpret_cast<TileCarry *>(static_cast<uint8_t *>(ctx->d_scratch) + sums_bytes);
-    int32_t *counts = copies || places ? reinterpret_cast<int32_t *>(static_cast<uint8_t *>(ctx->d_scratch) + sums_bytes + carries_bytes) : nullptr;
-    uint2 *lists = reinterpret_cast<uint2 *>(static_cast<uint8_t *>(ctx->d_scratch) + sums_bytes + carries_bytes + counts_bytes);
-    uint8_t *pk = reinterpret_cast<uint8_t *>(((uintptr_t)lists + lists_bytes + 63) & ~(uintptr_t)63);
-    uint32_t *cands = reinterpret_cast<uint32_t *>(pk);
-    int32_t *work = reinterpret_cast<int32_t *>(pk + cands_bytes), *pkcounts = reinterpret_cast<int32_t *>(pk + 2 * cands_bytes);
-    PkRec *recs = reinterpret_cast<PkRec *>(pk + 2 * cands_bytes + 2 * kScanJobs * sizeof(int32_t));
-    uint8_t *block = static_cast<uint8_t *>(d_block);
-    if (tiles) hipLaunchKernelGGL(bitscan_tile_kernel, dim3((unsigned)tiles), dim3(kLanes), 0, ctx->stream, J, block, sums);
-    hipLaunchKernelGGL(bitscan_combine_kernel, dim3(njobs), dim3(64), 0, ctx->stream, J, block, sums, carries, counts);
+    ScanScratch s;
+    if (int rc = scan_scratch(ctx, kScanJobs, tiles, copies, places, 0, &s)) return rc;
     bool any = false;
     for (int j = 0; j < njobs; ++j) any = any || ((h_jobs[j].codec_kind == 0 || h_jobs[j].packets) && h_jobs[j].n > 0);
-    if (any) hipLaunchKernelGGL(bitscan_emit_kernel, dim3((unsigned)tiles), dim3(kLanes), 0, ctx->stream, J, block, carries, lists, cands);
-    if (copies) hipLaunchKernelGGL(bitscan_frames_kernel, dim3(kFrameWaves, njobs), dim3(64), 0, ctx->stream, J, block, lists, counts);
-    if (places) {
-        const int ptune = ctx->tune.bitscan_packet_waves;
-        hipLaunchKernelGGL(bitscan_headers_kernel, dim3(njobs), dim3(64), 0, ctx->stream, J, block, counts, cands, recs, work, pkcounts);
-        hipLaunchKernelGGL(bitscan_blocks_kernel, dim3(ptune > 0 ? std::min(ptune, 1024) : kPacketWaves, njobs), dim3(64), 0, ctx->stream, J, block, recs, work, pkcounts);
+    scan_launch(ctx, J, njobs, tiles, copies, places, any, static_cast<uint8_t *>(d_block), s, kFrameWaves, kPacketWaves);
+    PM_HIP(hipGetLastError());
+    return PM_OK;
+}
+
+extern "C" int pm_rows_scan(pm_ctx *ctx, const pm_rowslice_rec *d_recs, const uint8_t *d_data, const uint16_t *d_steps, int64_t cap, int64_t row0, int nrows,
+                            const pm_rows_scan_chain *h_chains, int nchains, const int64_t *h_counts, void *d_block, size_t block_bytes, int64_t *h_offsets,
+                            size_t *h_used)
+{
+    using namespace pm_rows;
+    PM_CTX(ctx);
+    PM_ARG(d_recs && d_data && d_steps && cap >= 0 && (cap & 7) == 0 && ((uintptr_t)d_data & 7) == 0 && ((uintptr_t)d_steps & 7) == 0 && row0 >= 0);
+    PM_ARG(nrows >= 1 && nrows <= kMaxRows && h_chains && nchains >= 1 && nchains <= kMaxChains && h_counts);
+    PM_ARG(d_block && ((uintptr_t)d_block & 7) == 0 && h_offsets && h_used);
+    RowJobs J;
+    memset(&J, 0, sizeof(J));
+    J.data = d_data;
+    J.steps = d_steps;
+    J.cap = cap;
+    J.row0 = row0;
+    J.nrows = nrows;
+    J.nchains = nchains;
+    const int tune = ctx->tune.bitscan_tile_words;
+    J.tile_words = tune > 0 ? std::min(tune, kLanes) : kLanes;
+    const int ftune = ctx->tune.bitscan_frame_words;
+    J.frame_words = ftune > 0 ? std::min(ftune, 64) : 64;
+    for (int c = 0; c < nchains; ++c) {
+        const pm_rows_scan_chain &q = h_chains[c];
+        PM_ARG(q.codec_kind >= -1 && q.codec_kind <= 1);
+        PM_ARG(q.frames == 0 || (q.frames == 1 && q.codec_kind == 0));
+        PM_ARG(q.packets == 0 || (q.packets == 1 && q.codec_kind == 1));
+        J.poly[c] = q.lfsr_poly;
+        J.reg0[c] = q.lfsr_state;
+        J.kind[c] = (int8_t)q.codec_kind;
+        J.invert[c] = q.lfsr_invert != 0;
+        J.tol[c] = (int8_t)std::max(-1, std::min(33, q.sync_tol));
+        J.frames[c] = (int8_t)q.frames;
+        J.packets[c] = (int8_t)q.packets;
+        // (a min_dist below 0 corrects what 0 does, one above 8 nothing: the locator has eight roots at most)
+        J.pkopt[c] = (uint8_t)((q.il2p_crc != 0) | (q.il2p_disable_rs != 0) << 1 | std::max(0, std::min(9, q.il2p_min_dist)) << 2);
     }
+    // the host's copy of the sums, for the sizes: the device makes its own from the records
+    Sums all = sums_zero();
+    bool any = false;
+    for (int r = 0; r < nrows; ++r) {
+        const pm_rows_scan_chain &q = h_chains[(row0 + r) % nchains];
+        const int64_t n = h_counts[r];
+        PM_ARG(n >= 0 && n <= cap && n <= kMaxBytes);
+        h_offsets[r] = all.off;
+        all = sums_add(all, row_sums(q.codec_kind, q.frames, q.packets, n, J.tile_words));
+        PM_ARG(all.tiles < (int64_t)1 << 30);
+        any = any || ((q.codec_kind == 0 || q.packets) && n > 0);
+    }
+    *h_used = (size_t)all.off;
+    if ((size_t)all.off > block_bytes) return pm_set_error(PM_ERR_CAPACITY, "pm_rows_scan: the block holds %zu bytes, the rows need %zu", block_bytes, (size_t)all.off);
+    ScanScratch s;
+    if (int rc = scan_scratch(ctx, (size_t)nrows, all.tiles, all.events, all.places, ((size_t)nrows + 1) * sizeof(Entry), &s)) return rc;
+    Entry *table = reinterpret_cast<Entry *>(s.extra);
+    J.table = table;
+    hipLaunchKernelGGL(rows_prepare_kernel, dim3(1), dim3(kLanes), 0, ctx->stream, J, d_recs, table, all);
+    scan_launch(ctx, J, nrows, all.tiles, all.events, all.places, any, static_cast<uint8_t *>(d_block), s, kRowFrameWaves, kRowPacketWaves);
     PM_HIP(hipGetLastError());
     return PM_OK;
 }

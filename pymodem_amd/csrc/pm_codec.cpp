@@ -1243,7 +1243,7 @@ int pm_host_decode_batch(pm_host_job *jobs, int njobs, int threads)
     if (njobs < 0 || (njobs > 0 && !jobs) || threads < 1) return pm_set_error(PM_ERR_ARG, "pm_host_decode_batch: bad argument");
     for (int j = 0; j < njobs; ++j) {
         const pm_host_job &q = jobs[j];
-        if (!q.codec || q.n < 0 || (q.n > 0 && (!q.h_data || (!q.h_addr && !q.h_addr_delta))))
+        if (!q.codec || q.n < 0 || (q.n > 0 && ((!q.h_data && !q.h_scan) || (!q.h_addr && !q.h_addr_delta))))      // (with h_scan the bytes come from the block)
             return pm_set_error(PM_ERR_ARG, "pm_host_decode_batch: job %d: bad argument", j);
         for (int i = 0; i < j; ++i)
             if (jobs[i].codec == q.codec) return pm_set_error(PM_ERR_ARG, "pm_host_decode_batch: jobs %d and %d share a codec", i, j);

@@ -62,6 +62,15 @@ int pm_ctx_tune(pm_ctx *c, const char *name, int64_t value)
     return pm_set_error(PM_ERR_ARG, "pm_ctx_tune: no switch named '%s'", name);
 }
 
+int pm_ctx_tuned(pm_ctx *c, const char *name, int64_t *h_value)
+{
+    PM_ARG(c != nullptr && name != nullptr && h_value != nullptr);
+    if (!strcmp(name, "loop_lds_min")) { *h_value = c->tune.loop_lds_min; return PM_OK; }
+    for (const TuneKey &k : kTuneKeys)
+        if (!strcmp(name, k.name)) { *h_value = c->tune.*(k.field); return PM_OK; }
+    return pm_set_error(PM_ERR_ARG, "pm_ctx_tuned: no switch named '%s'", name);
+}
+
 int pm_device_count(void)
 {
     int n = 0;

@@ -205,6 +205,12 @@ class Context:
             check(lib().pm_ctx_tune(self.handle, name.encode(), int(value)))
         return self
 
+    def tuned(self, name):
+        """The value of a switch as this context holds it now (pm_ctx_tuned): what it read from PM_<NAME> when it was made, or the last tune()."""
+        v = ctypes.c_int64()
+        check(lib().pm_ctx_tuned(self.handle, name.encode(), ctypes.byref(v)))
+        return v.value
+
     def profile(self, on=True):
         check(lib().pm_prof_enable(self._h, int(bool(on))))
 

@@ -11,6 +11,7 @@ for a list of recordings: engine -> all slicers in batches -> LFSR + codec per r
 Results are those of process_chain on every recording, bit for bit (tests/test_gpu_loopbatch.py).
 """
 import ctypes
+import threading
 
 import numpy as np
 
@@ -222,6 +223,8 @@ class SlicedRun:
     def __init__(self, ctx, data, steps, recs, cap, rows, nout):
         self.ctx, self.data, self.steps, self.recs, self.cap, self.rows, self.nout = ctx, data, steps, recs, cap, rows, nout
         self._records = None
+        self.copied = 0                                      # bytes that fetch() and fetch_scanned() have brought to the host (diagnosis)
+        self._copied_lock = threading.Lock()
 
     def records(self, copy_ctx=None):
         if self._records is None:
@@ -256,6 +259,8 @@ class SlicedRun:
             block = ctx.scratch((tag if tag is not None else ("sliced-run", id(self)), "dense"), room, np.uint8)
             check(lib().pm_rows_gather(ctx.handle, self.recs.ptr, self.data.ptr, self.steps.ptr, self.cap, row0, nrows, block.ptr, block.n))
             host = block.download(used, recycle=True, ctx=ctx, room=room)
+            with self._copied_lock:
+                self.copied += used
         for k in range(nrows):
             c, o = int(counts[k]), int(offs[k])
             if c == 0:
@@ -264,6 +269,43 @@ class SlicedRun:
             sw = (2 * c + 7) // 8 * 8
             out.append(AddressedArray.from_steps(host[o + sw:o + sw + c], host[o:o + 2 * c].view(np.uint16), int(recs["first_addr"][k])))
         return out
+
+    def fetch_scanned(self, row0, nrows, chains, frames, packets, copy_ctx=None, tag=None):
+        """fetch() with the bitstream stage on the device in front of the copy (pm_rows_scan): `chains` are the run's chains [name, modem,
+        slicer, stream, codec], row k a stream of chain k % len(chains) that starts from that chain's LFSR register; frames / packets: the
+        AX.25 chains' frame tables / the IL2P chains' packet tables too.  -> per row (address steps, first address, n, the row's scan part
+        -- record, list, descrambled bytes, tables -- as views of one host block): one scan and ONE copy to the host for the lot."""
+        ctx = copy_ctx or self.ctx
+        recs = self.records()[row0:row0 + nrows]
+        counts = np.ascontiguousarray(np.minimum(recs["count"], self.cap), dtype=np.int64)
+        nchains = len(chains)
+        desc = (N.RowsScanChain * nchains)()
+        for d, ch in zip(desc, chains):
+            lfsr, codec = ch[3], ch[4]
+            d.lfsr_poly, d.lfsr_state, d.lfsr_invert = lfsr.polynomial, lfsr.shift_register, int(bool(lfsr.invert))
+            d.codec_kind, d.sync_tol = int(codec._kind), int(codec.sync_tolerance)
+            d.frames, d.packets = int(bool(frames) and codec._kind == 0), int(bool(packets) and codec._kind == 1)
+            d.il2p_crc, d.il2p_disable_rs, d.il2p_min_dist = int(codec.collect_trailing_crc), int(codec.disable_rs), int(codec.min_distance)
+        of = [desc[(row0 + k) % nchains] for k in range(nrows)]
+        parts = [N.scan_part_bytes(d.codec_kind, d.frames, d.packets, int(c)) for d, c in zip(of, counts)]
+        used = int(sum(N.rows_scan_steps_bytes(int(c)) for c in counts) + sum(parts))
+        # (the same 8 MB size classes as fetch(): the groups of a run ask for the same class and the page-locked blocks go round)
+        room = (used + (8 << 20) - 1) // (8 << 20) * (8 << 20)
+        block = ctx.scratch((tag if tag is not None else ("sliced-run", id(self)), "scanned"), room, np.uint8)
+        offs, need = (ctypes.c_int64 * nrows)(), ctypes.c_size_t()
+        check(lib().pm_rows_scan(ctx.handle, self.recs.ptr, self.data.ptr, self.steps.ptr, self.cap, row0, nrows, desc, nchains,
+                                 counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), block.ptr, block.n, offs, ctypes.byref(need)))
+        assert need.value == used, "pm_rows_scan and _native.scan_part_bytes size a row alike"
+        host = block.download(used, recycle=True, ctx=ctx, room=room)
+        with self._copied_lock:
+            self.copied += used
+        out = []
+        for k in range(nrows):
+            c, o = int(counts[k]), int(offs[k])
+            sw = N.rows_scan_steps_bytes(c)
+            out.append((host[o:o + 2 * c].view(np.uint16), int(recs["first_addr"][k]), c, host[o + sw:o + sw + parts[k]]))
+        return out
+
 
 
 _ENGINES = {}
@@ -287,20 +329,45 @@ def close_engines():
     _ENGINES.clear()
 
 
-def process_recordings_device(chain_sets, audios, ctx=None, chunk=0, rows=False, chain_ids=None, stages=None, slot=0, defer=False):
+def _scannable(chain_sets):
+    """The row form of the scan describes a chain once for all recordings: the library's own LFSR and codec objects, every recording's the
+    same and in the state they were made in (the codecs decode from the lists only from there)."""
+    from .lfsr import LFSR
+
+    def fresh(codec):                                         # (a native codec is made at its first use: none yet, nothing fed yet)
+        return codec._h is None
+
+    def what(ch):
+        lfsr, codec = ch[3], ch[4]
+        return (lfsr.polynomial, lfsr.shift_register, bool(lfsr.invert), codec._kind, bool(codec.collect_trailing_crc), bool(codec.disable_rs),
+                int(codec.min_distance), int(codec.sync_tolerance))
+    if not all(isinstance(ch[3], LFSR) and hasattr(ch[4], "_handle") and fresh(ch[4]) for cs in chain_sets for ch in cs):
+        return False
+    return len(chain_sets[0]) <= 64 and all(what(ch) == what(first) for cs in chain_sets for ch, first in zip(cs, chain_sets[0]))
+
+
+def process_recordings_device(chain_sets, audios, ctx=None, chunk=0, rows=False, chain_ids=None, stages=None, slot=0, defer=False, scan=None,
+                              frames=None, packets=None):
     """chain_sets[k] = the chains [name, modem, slicer, stream, codec] of recording k (every recording brings the same group of
     chains, as a service decoding successive recordings with one config does), audios[k] its int16 samples (host array or
     DeviceBuffer; equal lengths).  -> [[packets of chain 0, ...] per recording], identical to chain_execute.process_chain on each
     (rows=True: pm_packet rows instead of PacketMeta lists).  All carrier loops of all recordings advance together.
     defer=True: returns when the engine's run is complete, with a function that does the rest (the rows to the host, LFSR + codec) and
     returns the result -- a service calls it on another thread while this one starts the next batch's run (with the other `slot`): the
-    host's work on batch k then lies beside the GPU's on batch k + 1 instead of behind it."""
-    from .chain_execute import _host_rows, _host_stages, _pool
+    host's work on batch k then lies beside the GPU's on batch k + 1 instead of behind it.
+    scan / frames / packets (None: the context's switches pipe_scan, pipe_frames, pipe_packets, read from PM_PIPE_SCAN / FRAMES / PACKETS when
+    it was made; frames and packets imply scan): the bitstream stage of the fused-slicer route runs on the device, a group of rows per
+    pm_rows_scan (SlicedRun.fetch_scanned), and the codecs decode from its lists -- with frames the AX.25 chains' frames, with packets the
+    IL2P chains' headers and RS blocks come from there too.  Results are the same; stages["scanned"] says which way the decode went."""
+    from .chain_execute import _host_rows, _host_rows_scanned, _host_stages, _host_stages_scanned, _pool
     from .slicer import slice_batch
     ctx = ctx or Context.default()
     r = len(chain_sets)
     if r == 0:
         return (lambda: []) if defer else []
+    frames = bool(ctx.tuned("pipe_frames")) if frames is None else bool(frames)
+    packets = bool(ctx.tuned("pipe_packets")) if packets is None else bool(packets)
+    scan = (bool(ctx.tuned("pipe_scan")) if scan is None else bool(scan)) or frames or packets
     dev = []
     for a in audios:
         if isinstance(a, DeviceBuffer):
@@ -338,6 +405,8 @@ def process_recordings_device(chain_sets, audios, ctx=None, chunk=0, rows=False,
         t1 = time.perf_counter()
         run.records(Context.side(ctx.device, 399))          # (not on the context's own stream: the next run may be queued on it by now)
         if run.ok():
+            scanned = scan and _scannable(chain_sets)       # (foreign stream or codec objects, or codecs that have been used, go the old way)
+
             def rest():
                 for rec in range(r):
                     for c in range(nchains):
@@ -356,6 +425,18 @@ def process_recordings_device(chain_sets, audios, ctx=None, chunk=0, rows=False,
                     out = []
                     for lo in range(cuts[p], cuts[p + 1], per):
                         hi = min(lo + per, cuts[p + 1])
+                        if scanned:
+                            # the bitstream stage on the device in front of the copy; a recording's rows go to the codecs at once
+                            got = run.fetch_scanned(lo * nchains, (hi - lo) * nchains, chain_sets[0], frames, packets, sides[p], tag=("loop-sliced", p))
+                            for rec in range(lo, hi):
+                                mine = got[(rec - lo) * nchains:(rec - lo + 1) * nchains]
+                                if rows:
+                                    early[rec] = _pool().submit(_host_rows_scanned, chain_sets[rec], mine, chain_ids, frames, packets)
+                                else:
+                                    early[rec] = _pool().submit(_host_stages_scanned, chain_sets[rec], mine, frames, packets)
+                            if stages is not None:          # (diagnosis only: the slicers' bytes as the old way brings them)
+                                out += run.fetch(lo * nchains, (hi - lo) * nchains, sides[p], tag=("loop-sliced", p))
+                            continue
                         got = run.fetch(lo * nchains, (hi - lo) * nchains, sides[p], tag=("loop-sliced", p))
                         out += got
                         for rec in range(lo, hi):
@@ -369,6 +450,13 @@ def process_recordings_device(chain_sets, audios, ctx=None, chunk=0, rows=False,
                     stages["sliced"] = [sliced[rec * nchains:(rec + 1) * nchains] for rec in range(r)]
                     stages["seconds"] = {"engine": t1 - t0, "slicers": t2 - t1}
                     stages["fused_slicers"] = True
+                    stages["scanned"] = bool(scanned)
+                    stages["copied_bytes"] = run.copied     # (with the scan on: the plain fetch for stages["sliced"] counted too)
+                if scanned:
+                    out = [early[rec].result() for rec in range(r)]
+                    if stages is not None:
+                        stages["seconds"]["host"] = time.perf_counter() - t2
+                    return out
                 if rows:
                     out = [early[rec].result() for rec in range(r)]
                     if stages is not None:
