@@ -422,6 +422,13 @@ int pm_slice_compact(pm_ctx *ctx, const pm_slice_job *h_jobs, int njobs, void *d
  *       fit; chance headers and planted overlaps can run the area out.)
  * Two more launches: one wave per job takes the candidates 64 at a time, a lane a header; pm_ctx_tune(ctx, "bitscan_packet_waves", 1 .. 1024)
  * waves per job (0: 64) share the placed records' blocks.  Results do not depend on it.
+ * With pm_scan_job.addrs = 1 (any kind; d_addr: the n stream addresses that the slicer job left beside its bytes, pm_slice_job.d_addr;
+ * PM_ERR_ARG when it is NULL) one more piece follows everything above -- behind the frame or packet pieces when they are on -- and the
+ * pieces in front are byte for byte what they are without it:
+ *   the address checkpoints, PM_SCAN_ADDR_BYTES(n): (n + 63) / 64 places of 8 bytes, A[w] = the int64 stream address of data byte
+ *       PM_SCAN_ADDR_STRIDE * w.  With them and the 16-bit steps of pm_slice_compact the host resolves the address of byte k as A[k >> 6] plus
+ *       steps (k & ~63) + 1 .. k -- 63 additions at most -- where a decoder asks for one, and expands nothing (pm_codec_decode_addrs).
+ * No launch of its own: the tile launch's lanes store them, for tiles behind a bail too.
  * *h_used = bytes the batch needs; PM_ERR_CAPACITY (with *h_used set) if block_bytes is less.  n <= 2^29, njobs <= 64.  Tiles of
  * pm_ctx_tune(ctx, "bitscan_tile_words", 1 .. 256) 64-bit words (0: the default, 256); results do not depend on it. */
 #define PM_SCAN_HEAD 32
@@ -430,6 +437,8 @@ int pm_slice_compact(pm_ctx *ctx, const pm_slice_job *h_jobs, int njobs, void *d
 #define PM_SCAN_FRAME_AREA_BYTES(n) (((n) + 7) / 8 * 8)         /* ... and behind the table */
 #define PM_SCAN_PACKET_TABLE_BYTES(n) (16 + 16 * ((n) / 64 + 2))  /* packets: behind the descrambled bytes (padded to 8) ... */
 #define PM_SCAN_PACKET_AREA_BYTES(n) (((n) + 7) / 8 * 8)          /* ... and behind the table */
+#define PM_SCAN_ADDR_STRIDE 64                                    /* addrs: a checkpoint per this many data bytes ... */
+#define PM_SCAN_ADDR_BYTES(n) (8 * (((n) + 63) / 64))             /* ... behind everything else of the job's part */
 typedef struct pm_scan_job {
     const uint8_t *d_data;
     int64_t n;
@@ -441,6 +450,8 @@ typedef struct pm_scan_job {
     int32_t frames;                  /* 1 (kind 0 only): the frame table and the frame area behind the descrambled bytes */
     int32_t packets;                 /* 1 (kind 1 only): the packet table and the packet area behind the descrambled bytes ... */
     int32_t il2p_crc, il2p_disable_rs, il2p_min_dist;      /* ... for a codec with these options (pm_codec_create) */
+    const int64_t *d_addr;           /* with addrs: the stream addresses of the n bytes, on the device */
+    int32_t addrs;                   /* 1 (any kind): the address checkpoints behind everything else of the part */
 } pm_scan_job;
 int pm_stream_scan(pm_ctx *ctx, const pm_scan_job *h_jobs, int njobs, void *d_block, size_t block_bytes, int64_t *h_offsets, size_t *h_used);
 /* How many chunks (= walkers) a batch is cut into on this ctx, within 1024..16384 samples per chunk; 0 restores the default 16384.
@@ -558,10 +569,16 @@ int pm_rows_gather(pm_ctx *ctx, const pm_rowslice_rec *d_recs, const uint8_t *d_
  * pass block_bytes or what h_counts sized is left out.  Nothing is uploaded, allocated beyond the context's scratch or waited for;
  * d_block (8-byte aligned) may be page-locked host memory.  nrows <= 4096, nchains <= 64, n <= 2^29; PM_ERR_CAPACITY with *h_used set as in
  * pm_stream_scan.  The tunes bitscan_tile_words, bitscan_frame_words and bitscan_packet_waves mean what they mean there (by default a row's
- * events are shared by 16 waves and its placed records by 8); results do not depend on them. */
+ * events are shared by 16 waves and its placed records by 8); results do not depend on them.
+ * With pm_rows_scan_chain.addrs = 1 the rows of that chain get the address checkpoints of pm_scan_job.addrs at the end of their part,
+ * PM_SCAN_ADDR_BYTES(n): A[w] = d_recs[row].first_addr + steps[1] + ... + steps[64 w] over the row's steps at d_steps + row * cap -- a prefix
+ * sum in three steps: the tile launch sums each tile's steps, the combine launch carries an int64 prefix from tile to tile, one more small
+ * launch scans the lanes of every tile and stores.  A row that is left out gets none; the checkpoints of a row whose record has flag bit 0
+ * mean as little as its steps do. */
 typedef struct pm_rows_scan_chain {
     uint64_t lfsr_poly, lfsr_state;
     int32_t lfsr_invert, codec_kind, sync_tol, frames, packets, il2p_crc, il2p_disable_rs, il2p_min_dist;
+    int32_t addrs;                   /* 1: the address checkpoints at the end of the row's part */
 } pm_rows_scan_chain;
 int pm_rows_scan(pm_ctx *ctx, const pm_rowslice_rec *d_recs, const uint8_t *d_data, const uint16_t *d_steps, int64_t cap, int64_t row0, int nrows,
                  const pm_rows_scan_chain *h_chains, int nchains, const int64_t *h_counts, void *d_block, size_t block_bytes, int64_t *h_offsets,
@@ -636,6 +653,18 @@ int pm_codec_decode_framed(pm_codec *c, const uint8_t *h_plain, const int64_t *h
  * that cannot belong to the stream: records above the places or placed above records, `at` not ascending or k outside [4, n), count > 1023,
  * a placed record outside the area, an attempt that ends behind the stream, a DONE record whose header bytes say another count. */
 int pm_codec_decode_packets(pm_codec *c, const uint8_t *h_plain, const int64_t *h_addr, int64_t n, const void *h_scan, int64_t *h_pending);
+/* The three above for a part made with pm_scan_job.addrs (or pm_rows_scan_chain.addrs), without the n addresses: h_steps are the stream's n
+ * address steps in pm_slice_compact's form (uint16, address[i] - address[i - 1], the first one 0), addr_first the address of byte 0, and
+ * h_scan the part, whose last piece is the checkpoint table.  frames, packets: how the part was made (pm_scan_job.frames / .packets; at most
+ * one of them, and for the codec's kind) -- they say where the table lies and which way the codec goes: 0, 0 pm_codec_decode_scanned's,
+ * frames pm_codec_decode_framed's, packets pm_codec_decode_packets'.  Wherever those read h_addr[k], this resolves A[k >> 6] plus steps
+ * (k & ~63) + 1 .. k; packets, *h_pending and the codec's state are the same.  PM_ERR_ARG, with the codec untouched, for a table that
+ * cannot belong to the stream: A[0] != addr_first, a place below the one in front of it, or more than 64 * 65535 above it. */
+int pm_codec_decode_addrs(pm_codec *c, const uint8_t *h_plain, const uint16_t *h_steps, int64_t addr_first, int64_t n, const void *h_scan, int32_t frames,
+                          int32_t packets, int64_t *h_pending);
+/* Addresses this codec has resolved from a checkpoint so far, and the 16-bit steps it added for them (either may be NULL): at most 63 steps
+ * per look-up, and a look-up per queued packet or walked byte at the most. */
+int pm_codec_addr_work(pm_codec *c, int64_t *h_lookups, int64_t *h_steps);
 /* Bytes this codec has taken through its byte-by-byte machine so far, and bytes it has passed over (either may be NULL). */
 int pm_codec_walked(pm_codec *c, int64_t *h_walked, int64_t *h_jumped);
 
@@ -663,6 +692,8 @@ typedef struct pm_host_job {
                                   /* codec goes through pm_codec_decode_scanned (h_plain, if given, receives a copy of the bytes) */
     int32_t scan_frames;          /* with h_scan, AX.25 codecs only: the block was made with pm_scan_job.frames -> pm_codec_decode_framed */
     int32_t scan_packets;         /* with h_scan, IL2P codecs only: the block was made with pm_scan_job.packets -> pm_codec_decode_packets */
+    int32_t scan_addrs;           /* with h_scan, h_addr == NULL and h_addr_delta: the block was made with pm_scan_job.addrs -> the same route */
+                                  /* through pm_codec_decode_addrs: no address is expanded, each comes from its checkpoint where it is asked for */
 } pm_host_job;
 int pm_host_decode_batch(pm_host_job *jobs, int njobs, int threads);
 int pm_codec_fetch_batch(pm_codec *const *codecs, const int64_t *counts, int n, pm_packet *h_out, int threads);
@@ -708,7 +739,10 @@ int64_t pm_correlate_strided(void *h_records, int64_t stride, const int64_t *h_c
  * The switch pipe_frames (PM_PIPE_FRAMES, default 0) implies pipe_scan and has the AX.25 chains' jobs write their frames too
  * (pm_scan_job.frames, pm_host_job.scan_frames); IL2P chains go the pipe_scan way.  The switch pipe_packets (PM_PIPE_PACKETS, default 0),
  * independent of pipe_frames, implies pipe_scan and has the IL2P chains' jobs make their attempts on the device (pm_scan_job.packets with the
- * chain's codec options, pm_host_job.scan_packets).
+ * chain's codec options, pm_host_job.scan_packets).  The switch pipe_addrs (PM_PIPE_ADDRS, default 0), independent of both, implies pipe_scan
+ * and has every scan job write its address checkpoints (pm_scan_job.addrs from the slice job's d_addr, pm_host_job.scan_addrs): the host
+ * stage expands no addresses.  A recording whose flag bytes say that a step did not fit 16 bits keeps its full addresses, and keep_slices
+ * hands out full addresses as ever.
  * Results equal process_chain on every chain + PacketMetaArray.Correlate, recording by recording.  One submitting thread.  The
  * device pointers inside the descs (taps) must stay valid for the pipeline's life; host arrays are copied by pm_pipe_create. */
 typedef struct pm_pipe_fir {         /* a sign-FIR group: sign(FIR(int16 audio)) as one bitmap (pm_fir_signs_i16) -- FSKModem.demod, fsk.py:149-159 */

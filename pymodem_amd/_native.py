@@ -85,24 +85,28 @@ class HostJob(ctypes.Structure):
                 ("lfsr_poly", ctypes.c_uint64), ("lfsr_state", ctypes.c_uint64), ("pending", ctypes.c_int64),
                 ("lfsr_invert", ctypes.c_int32), ("status", ctypes.c_int32),
                 ("h_addr_delta", ctypes.c_void_p), ("addr_first", ctypes.c_int64), ("h_plain", ctypes.c_void_p),
-                ("h_scan", ctypes.c_void_p), ("scan_frames", ctypes.c_int32), ("scan_packets", ctypes.c_int32)]
+                ("h_scan", ctypes.c_void_p), ("scan_frames", ctypes.c_int32), ("scan_packets", ctypes.c_int32),
+                ("scan_addrs", ctypes.c_int32)]
 
 
 class ScanJob(ctypes.Structure):
     """pm_scan_job"""
     _fields_ = [("d_data", ctypes.c_void_p), ("n", ctypes.c_int64), ("lfsr_poly", ctypes.c_uint64), ("lfsr_state", ctypes.c_uint64),
                 ("lfsr_invert", ctypes.c_int32), ("codec_kind", ctypes.c_int32), ("sync_tol", ctypes.c_int32), ("frames", ctypes.c_int32),
-                ("packets", ctypes.c_int32), ("il2p_crc", ctypes.c_int32), ("il2p_disable_rs", ctypes.c_int32), ("il2p_min_dist", ctypes.c_int32)]
+                ("packets", ctypes.c_int32), ("il2p_crc", ctypes.c_int32), ("il2p_disable_rs", ctypes.c_int32), ("il2p_min_dist", ctypes.c_int32),
+                ("d_addr", ctypes.c_void_p), ("addrs", ctypes.c_int32)]
 
 
 class RowsScanChain(ctypes.Structure):
     """pm_rows_scan_chain"""
     _fields_ = [("lfsr_poly", ctypes.c_uint64), ("lfsr_state", ctypes.c_uint64),
                 ("lfsr_invert", ctypes.c_int32), ("codec_kind", ctypes.c_int32), ("sync_tol", ctypes.c_int32), ("frames", ctypes.c_int32),
-                ("packets", ctypes.c_int32), ("il2p_crc", ctypes.c_int32), ("il2p_disable_rs", ctypes.c_int32), ("il2p_min_dist", ctypes.c_int32)]
+                ("packets", ctypes.c_int32), ("il2p_crc", ctypes.c_int32), ("il2p_disable_rs", ctypes.c_int32), ("il2p_min_dist", ctypes.c_int32),
+                ("addrs", ctypes.c_int32)]
 
 
 SCAN_HEAD = 32        # PM_SCAN_HEAD
+SCAN_ADDR_STRIDE = 64  # PM_SCAN_ADDR_STRIDE
 
 
 def scan_list_bytes(kind, n):
@@ -130,13 +134,21 @@ def scan_packet_area_bytes(n):
     return (n + 7) // 8 * 8
 
 
-def scan_part_bytes(kind, frames, packets, n):
-    """What pm_stream_scan writes for a job of n bytes (pm_rows::scan_bytes): record, list, bytes, with frames or packets table and area."""
+def scan_addr_bytes(n):
+    """PM_SCAN_ADDR_BYTES: the address checkpoints of a job with `addrs` set, behind everything else of its part."""
+    return 8 * ((n + 63) // 64)
+
+
+def scan_part_bytes(kind, frames, packets, n, addrs=0):
+    """What pm_stream_scan writes for a job of n bytes (pm_rows::scan_bytes): record, list, bytes, with frames or packets table and area, with
+    addrs the address checkpoints behind them."""
     b = SCAN_HEAD + scan_list_bytes(kind, n) + (n + 7) // 8 * 8
     if frames:
         b += scan_frame_table_bytes(n) + scan_frame_area_bytes(n)
     if packets:
         b += scan_packet_table_bytes(n) + scan_packet_area_bytes(n)
+    if addrs:
+        b += scan_addr_bytes(n)
     return b
 
 
@@ -363,6 +375,8 @@ _SIGS = {
     "pm_codec_decode_framed": ([_vp, _vp, _vp, _i64, _vp, ctypes.POINTER(_i64)], _int),
     "pm_codec_decode_packets": ([_vp, _vp, _vp, _i64, _vp, ctypes.POINTER(_i64)], _int),
     "pm_codec_walked": ([_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)], _int),
+    "pm_codec_decode_addrs": ([_vp, _vp, _vp, _i64, _i64, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_i64)], _int),
+    "pm_codec_addr_work": ([_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)], _int),
     "pm_codec_fetch": ([_vp, _vp, _i64, ctypes.POINTER(_i64)], _int),
     "pm_host_decode_batch": ([ctypes.POINTER(HostJob), _int, _int], _int),
     "pm_codec_fetch_batch": ([ctypes.POINTER(_vp), ctypes.POINTER(_i64), _int, _vp, _int], _int),

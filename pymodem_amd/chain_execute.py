@@ -109,11 +109,11 @@ def _host_rows(chains, sliced, chain_ids=None):
     return views
 
 
-def _host_rows_scanned(chains, fetched, chain_ids=None, frames=False, packets=False):
+def _host_rows_scanned(chains, fetched, chain_ids=None, frames=False, packets=False, addrs=False):
     """_host_rows for rows that SlicedRun.fetch_scanned brought: fetched[j] = (address steps, first address, n, the row's scan part).  The
     LFSR has run on the device -- the descrambled bytes and the register come from the scan part (pm_host_job.h_scan, h_data = NULL) -- and the
     codecs, which must be in their just-created state, decode from its lists: AX.25 from the frame table when `frames`, IL2P from the
-    packet table when `packets`."""
+    packet table when `packets`.  addrs: the parts end with address checkpoints (pm_host_job.scan_addrs): no address is expanded."""
     import ctypes
     from ._native import HostJob, check, lib, packet_dtype, quick
     n = len(chains)
@@ -126,6 +126,7 @@ def _host_rows_scanned(chains, fetched, chain_ids=None, frames=False, packets=Fa
         jobs[j].h_addr_delta, jobs[j].addr_first = (steps.ctypes.data if count else None), int(first)
         jobs[j].h_scan = scan.ctypes.data
         jobs[j].scan_frames, jobs[j].scan_packets = int(bool(frames) and ch[4]._kind == 0), int(bool(packets) and ch[4]._kind == 1)
+        jobs[j].scan_addrs = int(bool(addrs))
         jobs[j].lfsr_poly, jobs[j].lfsr_state, jobs[j].lfsr_invert = ch[3].polynomial, ch[3].shift_register, int(bool(ch[3].invert))
     threads = _host_threads()
     rc = lib().pm_host_decode_batch(jobs, n, threads)
@@ -143,10 +144,10 @@ def _host_rows_scanned(chains, fetched, chain_ids=None, frames=False, packets=Fa
     return views
 
 
-def _host_stages_scanned(chains, fetched, frames=False, packets=False):
+def _host_stages_scanned(chains, fetched, frames=False, packets=False, addrs=False):
     """_host_stages for every chain of a recording from fetch_scanned's rows: PacketMeta lists."""
     from .packet_meta import rows_to_packets
-    return [rows_to_packets(v, ch[4].identifier) for ch, v in zip(chains, _host_rows_scanned(chains, fetched, None, frames, packets))]
+    return [rows_to_packets(v, ch[4].identifier) for ch, v in zip(chains, _host_rows_scanned(chains, fetched, None, frames, packets, addrs))]
 
 
 _POOL = None
@@ -886,7 +887,7 @@ class NativePipeline:
     raises ValueError for anything else (use RecordingPipeline there)."""
 
     def __init__(self, chains, max_samples, address_distance, ctx=None, names=None, chain_ids=None, slots=0, slice_workers=0, slice_group=0,
-                 host_threads=0, decode_threads=0, slice_min_group=0, demod_streams=0, keep_slices=False, scan=False, frames=False, packets=False):
+                 host_threads=0, decode_threads=0, slice_min_group=0, demod_streams=0, keep_slices=False, scan=False, frames=False, packets=False, addrs=False):
         import os
         demod_streams = demod_streams or int(os.environ.get("PYMODEM_AMD_PIPE_DEMOD_STREAMS", 0))
         slots = slots or int(os.environ.get("PYMODEM_AMD_PIPE_SLOTS", 0))              # tuning knobs (DESIGN.md 4.4b)
@@ -966,7 +967,8 @@ class NativePipeline:
         # scan: the bitstream stage on the device (pm_stream_scan behind the slicers, the codecs decode from its lists).  pm_pipe_create
         # reads the switch from its context.  frames: that, and the AX.25 chains' frames (de-stuffed bytes and CRC) come from the device too.
         # packets: that, and the IL2P chains' attempts (headers and RS blocks) are made on the device too
-        on = {k: 1 for k, v in (("pipe_scan", scan), ("pipe_frames", frames), ("pipe_packets", packets)) if v}
+        # addrs: that, and every scan job writes address checkpoints from which the host stage resolves the few addresses it needs
+        on = {k: 1 for k, v in (("pipe_scan", scan), ("pipe_frames", frames), ("pipe_packets", packets), ("pipe_addrs", addrs)) if v}
         ctx.tune(**on)
         try:
             check(lib().pm_pipe_create(ctx.handle, ctypes.byref(desc), ctypes.byref(h)))

@@ -19,7 +19,12 @@
 // The kernels take their jobs from a source that is a template parameter: pm_stream_scan's table of up to 64 jobs, passed by value, or
 // pm_rows_scan's row table for up to 4096 rows of a sliced engine run, which a small prepare launch makes in scratch from the rows' records
 // (pm_bitscan_rows.h).  Either hands a kernel one Job; the launches, their order and what they write for a job are the same.
+// With pm_scan_job.addrs / pm_rows_scan_chain.addrs the part ends with the address checkpoints (pm_bitscan_addrs.h), an int64 per 64 data
+// bytes.  The job form has the slicer's full addresses on the device: the tile launch's lane of every eighth word stores its byte's.  The
+// row form has 16-bit steps: the tile launch leaves each tile's sum of steps with its summary, the combine launch's wave carries an int64
+// prefix from tile to tile, and a small launch of its own scans the lanes of every tile and stores (rows_addrs_kernel).
 #include "pm_common.h"
+#include "pm_bitscan_addrs.h"
 #include "pm_bitscan_events.h"
 #include "pm_bitscan_frames.h"
 #include "pm_bitscan_rows.h"
@@ -44,6 +49,8 @@ struct Job {
     int kind, invert, tol;
     int pkopt;
     bool ok;                                // false: the job is left out, nothing is stored for it (rows only)
+    const int64_t *addr;                    // the job form's addrs: the n stream addresses, nullptr: no checkpoints
+    bool ckpt;                              // the row form's addrs: checkpoints from the row's steps
 };
 
 struct ScanJobs {
@@ -54,10 +61,11 @@ struct ScanJobs {
     int32_t tile0[kScanJobs + 1];           // first tile of the job among the batch's
     int8_t kind[kScanJobs], invert[kScanJobs], tol[kScanJobs];
     int32_t njobs, tile_words;
-    int64_t ev0[kScanJobs];                 // frames: the job's first place in the device-side copy of the lists, -1: no frames
+    int32_t ev0[kScanJobs];                 // frames: the job's first place in the device-side copy of the lists (below 64 (2^29 / 19 + 2)), -1: no frames
     int32_t frame_words;
     int32_t pk0[kScanJobs];                 // packets: the job's first place in the device-side candidate list, records and work list, -1: no packets
     uint8_t pkopt[kScanJobs];               // packets: the codec's crc | disable_rs << 1 | min_dist (0 .. 9) << 2
+    const int64_t *addr[kScanJobs];         // addrs: the job's stream addresses, nullptr: no checkpoints
 
     __device__ int tiles() const { return tile0[njobs]; }
     __device__ int job_of_tile(int tile) const
@@ -68,10 +76,13 @@ struct ScanJobs {
     }
     __device__ Job job(int j) const
     {
-        return Job{data[j], poly[j], reg0[j], off[j], ev0[j], pk0[j], n[j], tile0[j], tile0[j + 1], kind[j], invert[j], tol[j], pkopt[j], true};
+        return Job{data[j], poly[j], reg0[j], off[j], ev0[j], pk0[j], n[j], tile0[j], tile0[j + 1], kind[j], invert[j], tol[j], pkopt[j], true,
+                   addr[j], false};
     }
     __device__ void copy_steps(uint8_t *, const Job &, int, int64_t) const {}      // (the job form's block has no steps)
+    __device__ void load_steps(int, int64_t, uint64_t *, uint64_t *) const {}
 };
+static_assert(sizeof(ScanJobs) + 64 <= 4096, "the table goes to the kernels by value, with up to eight pointers beside it");
 
 // pm_rows_scan's source: the row table that the prepare launch leaves in scratch (pm_bitscan_rows.h), the rows' bytes where
 // pm_lbatch_run_sliced left them, and the chains' parameters by value.  Row r of the call is a stream of chain (row0 + r) % nchains.
@@ -84,6 +95,8 @@ struct RowJobs {
     int8_t kind[pm_rows::kMaxChains], invert[pm_rows::kMaxChains], tol[pm_rows::kMaxChains], frames[pm_rows::kMaxChains], packets[pm_rows::kMaxChains];
     uint8_t pkopt[pm_rows::kMaxChains];
     int32_t nrows, nchains, tile_words, frame_words;
+    int8_t addrs[pm_rows::kMaxChains];
+    const pm_rowslice_rec *recs;            // addrs: the rows' first addresses
 
     __device__ int tiles() const { return table[nrows].tile0; }
     __device__ int job_of_tile(int tile) const
@@ -96,7 +109,14 @@ struct RowJobs {
         const pm_rows::Entry e = table[j];
         const int c = (int)((row0 + j) % nchains);
         return Job{data + (row0 + j) * cap, poly[c], reg0[c], e.off + pm_rows::steps_bytes(e.n), e.ev0, e.pk0, e.n, e.tile0, table[j + 1].tile0,
-                   kind[c], invert[c], tol[c], pkopt[c], e.off >= 0};
+                   kind[c], invert[c], tol[c], pkopt[c], e.off >= 0, nullptr, addrs[c] != 0};
+    }
+    // the eight steps of data word w of row j (8 w < n <= cap, and cap is a multiple of 8: they lie inside the row)
+    __device__ void load_steps(int j, int64_t w, uint64_t *lo, uint64_t *hi) const
+    {
+        const uint64_t *src = reinterpret_cast<const uint64_t *>(steps + (row0 + j) * cap);
+        *lo = src[2 * w];
+        *hi = src[2 * w + 1];
     }
     // the row's address steps in front of its scan part, as pm_rows_gather writes them: the lane of data word w takes step words 2 w and 2 w + 1
     __device__ void copy_steps(uint8_t *block, const Job &jb, int j, int64_t w) const
@@ -221,6 +241,11 @@ struct TileSumLds {
 };
 
 __host__ __device__ inline int64_t list_bytes(int kind, int64_t n) { return PM_SCAN_LIST_BYTES(kind, n); }
+// the job's checkpoint table: behind everything else of its part
+__device__ inline int64_t *addr_table(uint8_t *block, const Job &jb)
+{
+    return reinterpret_cast<int64_t *>(block + jb.off + pm_rows::scan_bytes(jb.kind, jb.ev0 >= 0, jb.pk0 >= 0, jb.n));
+}
 
 // Launch 1: per tile the descrambled bytes, the IL2P bitmap, the tile's summary.
 template <class Jobs>
@@ -240,6 +265,7 @@ __global__ __launch_bounds__(kLanes) void bitscan_tile_kernel(Jobs J, uint8_t *b
     const uint8_t *d = jb.data;
     uint8_t *base = block + jb.off, *list = base + PM_SCAN_HEAD, *plain = list + list_bytes(kind, n);
     uint64_t x = 0, xp = 0, valid = 0;
+    uint32_t steps_sum = 0;                                 // the row form's addrs: the lane's eight steps
     if (active) {
         const uint64_t i0 = load_word(d, n, w), i1 = load_word(d, n, w - 1), i2 = load_word(d, n, w - 2);
         valid = valid_bits(n, w);
@@ -247,12 +273,20 @@ __global__ __launch_bounds__(kLanes) void bitscan_tile_kernel(Jobs J, uint8_t *b
         xp = w ? plain_word(jb, w - 1, i1, i2) : 0;           // (a fresh decoder: zeros in front of the stream)
         *reinterpret_cast<uint64_t *>(plain + 8 * w) = __builtin_bswap64(__brevll(x));       // the bytes are padded to 8: the last store is whole
         J.copy_steps(block, jb, j, w);
+        // the job form's checkpoints: byte 8 w is byte 64 (w / 8) and 8 w < n, so the place is one of the table's (n + 63) / 64
+        if (jb.addr && pm_addrs::owns_checkpoint(w)) addr_table(block, jb)[w >> 3] = jb.addr[8 * w];
+        if (jb.ckpt) {
+            uint64_t lo = 0, hi = 0;
+            J.load_steps(j, w, &lo, &hi);
+            steps_sum = pm_addrs::lane_sum(lo, hi, w, n);
+        }
     }
     if (threadIdx.x == 0) {
         ts = tile_sum_empty();
         ts.bail = kNoBail;
     }
     __syncthreads();
+    if (steps_sum) atomicAdd(&ts.steps, (int32_t)steps_sum);     // (at most 2048 x 65535: it fits)
     if (kind == 1) {
         // il2p.py:367-376 at the eight bit offsets of every byte k >= 4: the 32 bits in front of each against both patterns
         if (active) {
@@ -288,7 +322,8 @@ __global__ __launch_bounds__(kLanes) void bitscan_tile_kernel(Jobs J, uint8_t *b
 
 // Launch 2: a wave per stream takes the summaries in order, 64 at a time (a lane loads one, all lanes step through them together).
 template <class Jobs>
-__global__ __launch_bounds__(64) void bitscan_combine_kernel(Jobs J, uint8_t *block, const TileSum *sums, TileCarry *carries, int32_t *counts)
+__global__ __launch_bounds__(64) void bitscan_combine_kernel(Jobs J, uint8_t *block, const TileSum *sums, TileCarry *carries, int32_t *counts,
+                                                             int64_t *steps_before)
 {
     const int j = blockIdx.x, lane = threadIdx.x, tw = J.tile_words;
     const Job jb = J.job(j);
@@ -297,19 +332,29 @@ __global__ __launch_bounds__(64) void bitscan_combine_kernel(Jobs J, uint8_t *bl
     const int kind = jb.kind;
     Combine st = combine_start();
     int32_t cands = 0;
+    const bool ckpt = steps_before && jb.ckpt;              // the row form's addrs: the steps of the tiles in front of each tile, in 64 bits
+    int64_t steps = 0;
     for (int r0 = 0; r0 < nt; r0 += 64) {
         TileSum s = tile_sum_empty();
         if (r0 + lane < nt) s = sums[t0 + r0 + lane];
         TileCarry mine{0, -1, -1, 0, -1};
         for (int l = 0; l < 64 && r0 + l < nt; ++l) {
             const TileSum of{__shfl(s.dropped, l), __shfl(s.first_reset, l), __shfl(s.dropped_to_first, l), __shfl(s.last_reset, l), __shfl(s.dropped_after_last, l),
-                             __shfl(s.first_flag, l), __shfl(s.last_flag, l), __shfl(s.closing, l), __shfl(s.bail, l), __shfl(s.bits, l), {0, 0}};
+                             __shfl(s.first_flag, l), __shfl(s.last_flag, l), __shfl(s.closing, l), __shfl(s.bail, l), __shfl(s.bits, l), 0, 0};
             TileCarry c = kind == 0 ? combine_step(st, of, (int64_t)(r0 + l) * tw * 64) : combine_carry(st);
             if (kind == 1) c.events = cands;                // an IL2P tile: the candidates in front of it
             cands += of.closing;
             if (l == lane) mine = c;
         }
         if (r0 + lane < nt) carries[t0 + r0 + lane] = mine;
+        if (ckpt) {
+            int64_t mine_steps = 0;
+            for (int l = 0; l < 64 && r0 + l < nt; ++l) {
+                if (l == lane) mine_steps = steps;
+                steps += (int64_t)__shfl(s.steps, l);
+            }
+            if (r0 + lane < nt) steps_before[t0 + r0 + lane] = mine_steps;
+        }
     }
     if (lane == 0) {
         // the register as the stream leaves it (lfsr.py:30-51): what is left of the incoming one, and the taps of the last 63 input bits
@@ -711,6 +756,30 @@ __global__ __launch_bounds__(64) void bitscan_blocks_kernel(Jobs J, uint8_t *blo
     }
 }
 
+// The checkpoint launch of pm_rows_scan (pm_rows_scan_chain.addrs), behind the combine: a workgroup a tile, a lane a data word, as in the tile
+// launch.  The lanes load their eight steps again, one scan over the lanes gives each the steps of the tile's lanes in front, and the lane of
+// every eighth word stores A[w / 8] = the row's first address + the combine's prefix for the tile + that + the step to its own first byte
+// (pm_bitscan_addrs.h).  Every tile of every kind, behind a bail too; the emit launch covers neither.
+__global__ __launch_bounds__(kLanes) void rows_addrs_kernel(RowJobs J, uint8_t *block, const int64_t *steps_before)
+{
+    __shared__ uint32_t lds[kLanes];
+    const int tile = blockIdx.x, tw = J.tile_words;
+    if (tile >= J.tiles()) return;
+    const int j = J.job_of_tile(tile);
+    const Job jb = J.job(j);
+    if (!jb.ok || !jb.ckpt) return;
+    const int64_t n = jb.n, nw = (n + 7) / 8;
+    const int64_t w = (int64_t)(tile - jb.tile0) * tw + threadIdx.x;
+    const bool active = (int)threadIdx.x < tw && w < nw;
+    uint64_t lo = 0, hi = 0;
+    if (active) J.load_steps(j, w, &lo, &hi);
+    block_scan(active ? pm_addrs::lane_sum(lo, hi, w, n) : 0u, lds, [](uint32_t a, uint32_t b) { return a + b; });
+    const uint32_t before = threadIdx.x ? lds[threadIdx.x - 1] : 0u;
+    // (8 w < n: the place is one of the table's (n + 63) / 64)
+    if (active && pm_addrs::owns_checkpoint(w))
+        addr_table(block, jb)[w >> 3] = pm_addrs::checkpoint(J.recs[J.row0 + j].first_addr, steps_before[tile], before, pm_addrs::lane_first(lo, w));
+}
+
 // The prepare launch of pm_rows_scan: the row table from the records' counts and the chains' kinds (pm_bitscan_rows.h) -- one workgroup,
 // trips of 256 rows, a lane a row: an inclusive scan of the rows' four sums over the lanes, the carry from trip to trip.
 __global__ __launch_bounds__(kLanes) void rows_prepare_kernel(RowJobs J, const pm_rowslice_rec *recs, pm_rows::Entry *table, pm_rows::Sums limit)
@@ -723,12 +792,12 @@ __global__ __launch_bounds__(kLanes) void rows_prepare_kernel(RowJobs J, const p
         const int r = r0 + (int)threadIdx.x, c = (int)((J.row0 + r) % J.nchains);
         const bool active = r < J.nrows;
         const int64_t n = active ? row_bytes(recs[J.row0 + r].count, J.cap) : 0;
-        const Sums mine = active ? row_sums(J.kind[c], J.frames[c], J.packets[c], n < kMaxBytes ? n : kMaxBytes, J.tile_words) : sums_zero();
+        const Sums mine = active ? row_sums(J.kind[c], J.frames[c], J.packets[c], n < kMaxBytes ? n : kMaxBytes, J.tile_words, J.addrs[c]) : sums_zero();
         const Sums upto = block_scan(mine, lds, [](const Sums &a, const Sums &b) { return sums_add(a, b); });
         const Sums before = sums_add(carry, threadIdx.x ? lds[threadIdx.x - 1] : sums_zero());
         carry = sums_add(carry, lds[kLanes - 1]);
         (void)upto;
-        if (active) table[r] = row_entry(before, J.kind[c], J.frames[c], J.packets[c], n, J.tile_words, limit);
+        if (active) table[r] = row_entry(before, J.kind[c], J.frames[c], J.packets[c], n, J.tile_words, limit, J.addrs[c]);
         __syncthreads();
     }
     if (threadIdx.x == 0) table[J.nrows] = total_entry(carry, limit);
@@ -744,8 +813,9 @@ struct ScanScratch {
     int32_t *work, *pkcounts;
     PkRec *recs;
     uint8_t *extra;                         // `extra_bytes` behind everything, 64-byte aligned (the row table)
+    int64_t *steps_before;                  // the row form's addrs: per tile the steps of its row's tiles in front, nullptr: no checkpoints
 };
-int scan_scratch(pm_ctx *ctx, size_t jobs, int64_t tiles, int64_t copies, int64_t places, size_t extra_bytes, ScanScratch *out)
+int scan_scratch(pm_ctx *ctx, size_t jobs, int64_t tiles, int64_t copies, int64_t places, size_t extra_bytes, ScanScratch *out, bool steps_before = false)
 {
     const size_t sums_bytes = ((size_t)tiles * sizeof(TileSum) + 63) & ~(size_t)63;
     // (frames: the event counts and a copy of the lists stay on the device for the frames launch, behind the carries)
@@ -753,7 +823,8 @@ int scan_scratch(pm_ctx *ctx, size_t jobs, int64_t tiles, int64_t copies, int64_
     // (packets: the candidates, a copy of every record with its header bytes, the list of those with blocks to decode, and the two counts per job)
     const size_t lists_bytes = (size_t)copies * sizeof(uint2), cands_bytes = ((size_t)places * sizeof(uint32_t) + 63) & ~(size_t)63, recs_bytes = (size_t)places * sizeof(PkRec);
     const size_t pk_bytes = places ? 2 * cands_bytes + recs_bytes + 2 * jobs * sizeof(int32_t) : 0;
-    if (int rc = pm_scratch_reserve(ctx, sums_bytes + carries_bytes + counts_bytes + lists_bytes + pk_bytes + extra_bytes + 256)) return rc;
+    const size_t extra_padded = (extra_bytes + 63) & ~(size_t)63, before_bytes = steps_before ? (size_t)tiles * sizeof(int64_t) : 0;
+    if (int rc = pm_scratch_reserve(ctx, sums_bytes + carries_bytes + counts_bytes + lists_bytes + pk_bytes + extra_padded + before_bytes + 256)) return rc;
     uint8_t *base = static_cast<uint8_t *>(ctx->d_scratch);
     out->sums = reinterpret_cast<TileSum *>(base);
     out->carries = reinterpret_cast<TileCarry *>(base + sums_bytes);
@@ -765,6 +836,7 @@ int scan_scratch(pm_ctx *ctx, size_t jobs, int64_t tiles, int64_t copies, int64_
     out->pkcounts = reinterpret_cast<int32_t *>(pk + 2 * cands_bytes);
     out->recs = reinterpret_cast<PkRec *>(pk + 2 * cands_bytes + 2 * jobs * sizeof(int32_t));
     out->extra = reinterpret_cast<uint8_t *>(((uintptr_t)pk + pk_bytes + 63) & ~(uintptr_t)63);
+    out->steps_before = steps_before ? reinterpret_cast<int64_t *>(out->extra + extra_padded) : nullptr;
     return PM_OK;
 }
 
@@ -774,7 +846,7 @@ void scan_launch(pm_ctx *ctx, const Jobs &J, int njobs, int64_t tiles, int64_t c
                  int frame_waves, int packet_waves)
 {
     if (tiles) hipLaunchKernelGGL(bitscan_tile_kernel<Jobs>, dim3((unsigned)tiles), dim3(kLanes), 0, ctx->stream, J, block, s.sums);
-    hipLaunchKernelGGL(bitscan_combine_kernel<Jobs>, dim3(njobs), dim3(64), 0, ctx->stream, J, block, s.sums, s.carries, s.counts);
+    hipLaunchKernelGGL(bitscan_combine_kernel<Jobs>, dim3(njobs), dim3(64), 0, ctx->stream, J, block, s.sums, s.carries, s.counts, s.steps_before);
     if (emit && tiles) hipLaunchKernelGGL(bitscan_emit_kernel<Jobs>, dim3((unsigned)tiles), dim3(kLanes), 0, ctx->stream, J, block, s.carries, s.lists, s.cands);
     if (copies) hipLaunchKernelGGL(bitscan_frames_kernel<Jobs>, dim3(frame_waves, njobs), dim3(64), 0, ctx->stream, J, block, s.lists, s.counts);
     if (places) {
@@ -806,6 +878,8 @@ extern "C" int pm_stream_scan(pm_ctx *ctx, const pm_scan_job *h_jobs, int njobs,
         PM_ARG(q.codec_kind >= -1 && q.codec_kind <= 1);
         PM_ARG(q.frames == 0 || (q.frames == 1 && q.codec_kind == 0));
         PM_ARG(q.packets == 0 || (q.packets == 1 && q.codec_kind == 1));
+        PM_ARG(q.addrs == 0 || (q.addrs == 1 && q.d_addr && ((uintptr_t)q.d_addr & 7) == 0));
+        J.addr[j] = q.addrs ? q.d_addr : nullptr;
         J.data[j] = q.d_data;
         J.poly[j] = q.lfsr_poly;
         J.reg0[j] = q.lfsr_state;
@@ -819,8 +893,9 @@ extern "C" int pm_stream_scan(pm_ctx *ctx, const pm_scan_job *h_jobs, int njobs,
         J.ev0[j] = -1;
         if (q.frames) {
             at += (size_t)PM_SCAN_FRAME_TABLE_BYTES(q.n) + (size_t)PM_SCAN_FRAME_AREA_BYTES(q.n);
-            J.ev0[j] = copies;
+            J.ev0[j] = (int32_t)copies;
             copies += q.n / 19 + 2;
+            PM_ARG(copies < INT32_MAX);                     // (ev0 is 32 bits; 64 jobs of 2^29 bytes stay below it)
         }
         J.pk0[j] = -1;
         if (q.packets) {
@@ -830,6 +905,7 @@ extern "C" int pm_stream_scan(pm_ctx *ctx, const pm_scan_job *h_jobs, int njobs,
             J.pkopt[j] = (uint8_t)((q.il2p_crc != 0) | (q.il2p_disable_rs != 0) << 1 | std::max(0, std::min(9, q.il2p_min_dist)) << 2);
             places += q.n / 64 + 2;
         }
+        if (q.addrs) at += (size_t)PM_SCAN_ADDR_BYTES(q.n);   // behind everything else of the part
         tiles += pm_cdiv(pm_cdiv(q.n, 8), J.tile_words);
         PM_ARG(tiles < (int64_t)1 << 30);
     }
@@ -858,6 +934,7 @@ extern "C" int pm_rows_scan(pm_ctx *ctx, const pm_rowslice_rec *d_recs, const ui
     memset(&J, 0, sizeof(J));
     J.data = d_data;
     J.steps = d_steps;
+    J.recs = d_recs;
     J.cap = cap;
     J.row0 = row0;
     J.nrows = nrows;
@@ -871,6 +948,8 @@ extern "C" int pm_rows_scan(pm_ctx *ctx, const pm_rowslice_rec *d_recs, const ui
         PM_ARG(q.codec_kind >= -1 && q.codec_kind <= 1);
         PM_ARG(q.frames == 0 || (q.frames == 1 && q.codec_kind == 0));
         PM_ARG(q.packets == 0 || (q.packets == 1 && q.codec_kind == 1));
+        PM_ARG(q.addrs == 0 || q.addrs == 1);
+        J.addrs[c] = (int8_t)q.addrs;
         J.poly[c] = q.lfsr_poly;
         J.reg0[c] = q.lfsr_state;
         J.kind[c] = (int8_t)q.codec_kind;
@@ -883,24 +962,27 @@ extern "C" int pm_rows_scan(pm_ctx *ctx, const pm_rowslice_rec *d_recs, const ui
     }
     // the host's copy of the sums, for the sizes: the device makes its own from the records
     Sums all = sums_zero();
-    bool any = false;
+    bool any = false, any_addrs = false;
     for (int r = 0; r < nrows; ++r) {
         const pm_rows_scan_chain &q = h_chains[(row0 + r) % nchains];
+        any_addrs = any_addrs || q.addrs;
         const int64_t n = h_counts[r];
         PM_ARG(n >= 0 && n <= cap && n <= kMaxBytes);
         h_offsets[r] = all.off;
-        all = sums_add(all, row_sums(q.codec_kind, q.frames, q.packets, n, J.tile_words));
+        all = sums_add(all, row_sums(q.codec_kind, q.frames, q.packets, n, J.tile_words, q.addrs));
         PM_ARG(all.tiles < (int64_t)1 << 30);
         any = any || ((q.codec_kind == 0 || q.packets) && n > 0);
     }
     *h_used = (size_t)all.off;
     if ((size_t)all.off > block_bytes) return pm_set_error(PM_ERR_CAPACITY, "pm_rows_scan: the block holds %zu bytes, the rows need %zu", block_bytes, (size_t)all.off);
     ScanScratch s;
-    if (int rc = scan_scratch(ctx, (size_t)nrows, all.tiles, all.events, all.places, ((size_t)nrows + 1) * sizeof(Entry), &s)) return rc;
+    if (int rc = scan_scratch(ctx, (size_t)nrows, all.tiles, all.events, all.places, ((size_t)nrows + 1) * sizeof(Entry), &s, any_addrs)) return rc;
     Entry *table = reinterpret_cast<Entry *>(s.extra);
     J.table = table;
     hipLaunchKernelGGL(rows_prepare_kernel, dim3(1), dim3(kLanes), 0, ctx->stream, J, d_recs, table, all);
     scan_launch(ctx, J, nrows, all.tiles, all.events, all.places, any, static_cast<uint8_t *>(d_block), s, kRowFrameWaves, kRowPacketWaves);
+    if (any_addrs && all.tiles)
+        hipLaunchKernelGGL(rows_addrs_kernel, dim3((unsigned)all.tiles), dim3(kLanes), 0, ctx->stream, J, static_cast<uint8_t *>(d_block), s.steps_before);
     PM_HIP(hipGetLastError());
     return PM_OK;
 }

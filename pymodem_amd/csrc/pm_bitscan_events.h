@@ -29,9 +29,10 @@ struct TileSum {
     int32_t closing;                        // AX.25: closing flags whose reset lies inside the tile; IL2P: candidates
     int32_t bail;
     int32_t bits;                           // 1: the first reset is a flag, 2: the first flag is counted in `closing`
-    int32_t pad[2];
+    int32_t steps;                          // the row form's addrs: the sum of the tile's 16-bit steps (at most 2048 x 65535), else 0
+    int32_t pad;                            // (keeps the summary at 48 bytes)
 };
-PM_EV_HD TileSum tile_sum_empty() { return TileSum{0, -1, 0, -1, 0, -1, -1, 0, -1, 0, {0, 0}}; }
+PM_EV_HD TileSum tile_sum_empty() { return TileSum{0, -1, 0, -1, 0, -1, -1, 0, -1, 0, 0, 0}; }
 
 // What a tile starts from, left by the combine launch for the emit launch.
 struct TileCarry {

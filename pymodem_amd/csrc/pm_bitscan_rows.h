@@ -27,15 +27,20 @@ PM_ROWS_HD int64_t steps_bytes(int64_t n) { return pad8(2 * n); }           // t
 PM_ROWS_HD int64_t list_bytes(int kind, int64_t n) { return kind == 0 ? 8 * (n / 19 + 2) : kind == 1 ? 8 * ((n + 63) / 64) : 0; }      // PM_SCAN_LIST_BYTES
 PM_ROWS_HD int64_t row_events(int frames, int64_t n) { return frames ? n / 19 + 2 : 0; }       // places in the device-side copy of the event list
 PM_ROWS_HD int64_t row_places(int packets, int64_t n) { return packets ? n / 64 + 2 : 0; }     // places in the candidate, record and work lists
-// what pm_stream_scan writes for a job of these bytes: record, list, descrambled bytes, with frames or packets the table and the area
-PM_ROWS_HD int64_t scan_bytes(int kind, int frames, int packets, int64_t n)
+PM_ROWS_HD int64_t addr_bytes(int addrs, int64_t n) { return addrs ? 8 * ((n + 63) / 64) : 0; }     // PM_SCAN_ADDR_BYTES: the checkpoints, last in the part
+// what pm_stream_scan writes for a job of these bytes: record, list, descrambled bytes, with frames or packets the table and the area,
+// with addrs the address checkpoints behind all of them (scan_bytes(.., 0) is where they begin)
+PM_ROWS_HD int64_t scan_bytes(int kind, int frames, int packets, int64_t n, int addrs = 0)
 {
     int64_t b = kHead + list_bytes(kind, n) + pad8(n);
     if (frames) b += 8 * (n / 19 + 2) + pad8(n);            // PM_SCAN_FRAME_TABLE_BYTES, PM_SCAN_FRAME_AREA_BYTES
     if (packets) b += 16 + 16 * (n / 64 + 2) + pad8(n);     // PM_SCAN_PACKET_TABLE_BYTES, PM_SCAN_PACKET_AREA_BYTES
-    return b;
+    return b + addr_bytes(addrs, n);
 }
-PM_ROWS_HD int64_t part_bytes(int kind, int frames, int packets, int64_t n) { return steps_bytes(n) + scan_bytes(kind, frames, packets, n); }
+PM_ROWS_HD int64_t part_bytes(int kind, int frames, int packets, int64_t n, int addrs = 0)
+{
+    return steps_bytes(n) + scan_bytes(kind, frames, packets, n, addrs);
+}
 PM_ROWS_HD int64_t row_tiles(int64_t n, int tile_words) { return ((n + 7) / 8 + tile_words - 1) / tile_words; }
 
 // The four running sums.  As a row's own: what it adds; as a prefix: where it begins; over all rows: the limits the call was sized for.
@@ -44,9 +49,9 @@ struct Sums {
 };
 PM_ROWS_HD Sums sums_zero() { return Sums{0, 0, 0, 0}; }
 PM_ROWS_HD Sums sums_add(const Sums &a, const Sums &b) { return Sums{a.off + b.off, a.tiles + b.tiles, a.events + b.events, a.places + b.places}; }
-PM_ROWS_HD Sums row_sums(int kind, int frames, int packets, int64_t n, int tile_words)
+PM_ROWS_HD Sums row_sums(int kind, int frames, int packets, int64_t n, int tile_words, int addrs = 0)
 {
-    return Sums{part_bytes(kind, frames, packets, n), row_tiles(n, tile_words), row_events(frames, n), row_places(packets, n)};
+    return Sums{part_bytes(kind, frames, packets, n, addrs), row_tiles(n, tile_words), row_events(frames, n), row_places(packets, n)};
 }
 
 // A row of the device-side table.  Entry `nrows` holds the totals: its tile0 ends the last row's tiles.
@@ -59,9 +64,9 @@ struct Entry {
 };
 // `before`: the sums over the rows in front; `limit`: what the host sized block and scratch for from its own copy of the counts.  A row
 // that would pass any of them -- the records and the host's counts disagree -- is left out: no launch stores anything for it.
-PM_ROWS_HD Entry row_entry(const Sums &before, int kind, int frames, int packets, int64_t n, int tile_words, const Sums &limit)
+PM_ROWS_HD Entry row_entry(const Sums &before, int kind, int frames, int packets, int64_t n, int tile_words, const Sums &limit, int addrs = 0)
 {
-    const Sums end = sums_add(before, row_sums(kind, frames, packets, n < kMaxBytes ? n : kMaxBytes, tile_words));
+    const Sums end = sums_add(before, row_sums(kind, frames, packets, n < kMaxBytes ? n : kMaxBytes, tile_words, addrs));
     const bool ok = n <= kMaxBytes && end.off <= limit.off && end.tiles <= limit.tiles && end.events <= limit.events && end.places <= limit.places;
     return Entry{ok ? before.off : -1, frames ? before.events : -1, packets ? before.places : -1, (int32_t)(n < kMaxBytes ? n : kMaxBytes),
                  (int32_t)(before.tiles < limit.tiles ? before.tiles : limit.tiles)};

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/pymodem_amd.h"
+#include "pm_bitscan_addrs.h"
 #include "pm_il2p_core.h"
 
 int pm_set_error(int code, const char *fmt, ...);
@@ -153,6 +154,7 @@ struct pm_codec {
     bool fresh = true;                                   // nothing fed yet: the state pm_stream_scan's lists are made for
     int64_t walked = 0;                                  // bytes taken through the byte-by-byte machine (pm_codec_walked)
     int64_t fed = 0;
+    int64_t addr_lookups = 0, addr_steps = 0;            // addresses resolved from a checkpoint, and the 16-bit steps added for them (pm_codec_addr_work)
     virtual ~pm_codec() {}
     // feed_many for a fresh decoder with the stream's pm_stream_scan record and list; false: the list does not fit the stream
     virtual bool feed_scanned(const uint8_t *d, const int64_t *a, int64_t n, const uint8_t *scan) = 0;
@@ -160,6 +162,10 @@ struct pm_codec {
     virtual bool feed_framed(const uint8_t *, const int64_t *, int64_t, const uint8_t *) { return false; }
     // the same with the packet table and the packet area of a block made with pm_scan_job.packets (IL2P only)
     virtual bool feed_packets(const uint8_t *, const int64_t *, int64_t, const uint8_t *) { return false; }
+    // the three with the addresses behind checkpoints (pm_bitscan_addrs.h): the same text, instantiated for the look-up instead of the pointer
+    virtual bool feed_scanned(const uint8_t *d, pm_addrs::Ref a, int64_t n, const uint8_t *scan) = 0;
+    virtual bool feed_framed(const uint8_t *, pm_addrs::Ref, int64_t, const uint8_t *) { return false; }
+    virtual bool feed_packets(const uint8_t *, pm_addrs::Ref, int64_t, const uint8_t *) { return false; }
     virtual void feed(uint8_t byte, int64_t addr, Sink &sink) = 0;
     virtual void feed_many(const uint8_t *d, const int64_t *a, int64_t n)
     {
@@ -363,7 +369,10 @@ struct Ax25 : pm_codec {
 
     // feed_many with the events found on the device (pm_bitscan.hip): the same reposition / run calls in the same order, the flags that
     // close something read from the list instead of searched for
-    bool feed_scanned(const uint8_t *d, const int64_t *a, int64_t n, const uint8_t *scan) override
+    bool feed_scanned(const uint8_t *d, const int64_t *a, int64_t n, const uint8_t *scan) override { return scanned(d, a, n, scan); }
+    bool feed_scanned(const uint8_t *d, pm_addrs::Ref a, int64_t n, const uint8_t *scan) override { return scanned(d, a, n, scan); }
+    template <class A>                                   // A: const int64_t *, or pm_addrs::Ref
+    bool scanned(const uint8_t *d, A a, int64_t n, const uint8_t *scan)
     {
         if (!skim_on || n < 24) {
             run(d, a, 0, n);
@@ -399,7 +408,10 @@ struct Ax25 : pm_codec {
 
     // feed_scanned with the frames themselves from the device: every listed flag's frame is queued as the frame area holds it, and only
     // what lies behind the stream's last flag (or behind the last flag in front of a bail) goes through the registers
-    bool feed_framed(const uint8_t *d, const int64_t *a, int64_t n, const uint8_t *scan) override
+    bool feed_framed(const uint8_t *d, const int64_t *a, int64_t n, const uint8_t *scan) override { return framed(d, a, n, scan); }
+    bool feed_framed(const uint8_t *d, pm_addrs::Ref a, int64_t n, const uint8_t *scan) override { return framed(d, a, n, scan); }
+    template <class A>
+    bool framed(const uint8_t *d, A a, int64_t n, const uint8_t *scan)
     {
         if (!skim_on || n < 24) {
             run(d, a, 0, n);
@@ -433,7 +445,8 @@ struct Ax25 : pm_codec {
     }
 
     // bytes [k0, k1) through the registers, eight bits at a time (round 2)
-    void run(const uint8_t *d, const int64_t *a, int64_t k0, int64_t k1)
+    template <class A>
+    void run(const uint8_t *d, A a, int64_t k0, int64_t k1)
     {
         walked += k1 - k0;
         // the collected bytes as a raw buffer while this call runs (one slot of slack: a byte is stored whether or not it is
@@ -593,6 +606,11 @@ struct Il2p : pm_codec {
         feed_search(d, a, n, scan + PM_SCAN_HEAD);
         return true;
     }
+    bool feed_scanned(const uint8_t *d, pm_addrs::Ref a, int64_t n, const uint8_t *scan) override
+    {
+        feed_search(d, a, n, scan + PM_SCAN_HEAD);
+        return true;
+    }
 
     // pm_stream_scan's packet table (its places) and packet area while feed_packets runs: what feed_search looks a hit up in
     const uint8_t *pk_places = nullptr, *pk_area = nullptr;
@@ -600,7 +618,10 @@ struct Il2p : pm_codec {
 
     // feed_search with the records of the attempts that the device has made (pm_il2p_core.h, include/pymodem_amd.h): a hit of the decoder's
     // own register test whose record says what the attempt from there comes to is not walked.  false: the table cannot belong to the stream.
-    bool feed_packets(const uint8_t *d, const int64_t *a, int64_t n, const uint8_t *scan) override
+    bool feed_packets(const uint8_t *d, const int64_t *a, int64_t n, const uint8_t *scan) override { return packets(d, a, n, scan); }
+    bool feed_packets(const uint8_t *d, pm_addrs::Ref a, int64_t n, const uint8_t *scan) override { return packets(d, a, n, scan); }
+    template <class A>
+    bool packets(const uint8_t *d, A a, int64_t n, const uint8_t *scan)
     {
         using namespace pm_il2p;
         const uint8_t *table = scan + PM_SCAN_HEAD + PM_SCAN_LIST_BYTES(1, n) + ((n + 7) & ~int64_t(7)), *area = table + PM_SCAN_PACKET_TABLE_BYTES(n);
@@ -634,7 +655,8 @@ struct Il2p : pm_codec {
     // The register test has hit at byte k, offset i (the header starts at bit 8 k + i).  With a record for exactly that place whose attempt the
     // device has finished: what the attempt leaves behind -- a packet, a count of corrections, nothing -- and the rest of the byte in which it
     // ends through the machine; returns that byte.  -1: no such record, the machine takes it from here as ever.
-    int64_t take_record(const uint8_t *d, const int64_t *a, int64_t k, int i)
+    template <class A>
+    int64_t take_record(const uint8_t *d, A a, int64_t k, int i)
     {
         using namespace pm_il2p;
         Rec r{};
@@ -690,7 +712,8 @@ struct Il2p : pm_codec {
     }
 
     // cand: nullptr, or pm_stream_scan's bitmap of the bytes at which the sync test hits on the INPUT's last 40 bits
-    void feed_search(const uint8_t *d, const int64_t *a, int64_t n, const uint8_t *cand)
+    template <class A>
+    void feed_search(const uint8_t *d, A a, int64_t n, const uint8_t *cand)
     {
         int64_t skipped = 0;
         for (int64_t k = 0; k < n; ++k) {
@@ -1195,6 +1218,43 @@ int pm_codec_decode_packets(pm_codec *c, const uint8_t *h_plain, const int64_t *
     return PM_OK;
 }
 
+// The three scanned routes with the addresses behind the part's checkpoint table: what the pointer forms above do, instantiated for the
+// look-up.  The table is checked first -- O(n / 64) -- and a refusal leaves the codec untouched.
+int pm_codec_decode_addrs(pm_codec *c, const uint8_t *h_plain, const uint16_t *h_steps, int64_t addr_first, int64_t n, const void *h_scan, int32_t frames,
+                          int32_t packets, int64_t *h_pending)
+{
+    if (!c || n < 0 || (n > 0 && (!h_plain || !h_steps)) || !h_scan || !h_pending || (frames && packets))
+        return pm_set_error(PM_ERR_ARG, "pm_codec_decode_addrs: bad argument");
+    if ((frames && c->kind != 0) || (packets && c->kind != 1))
+        return pm_set_error(PM_ERR_ARG, "pm_codec_decode_addrs: frames are made for AX.25 codecs only, packets for IL2P codecs only");
+    if (!c->fresh) return pm_set_error(PM_ERR_ARG, "pm_codec_decode_addrs: the codec has been fed before (the lists are made for a just-created decoder)");
+    const uint8_t *scan = static_cast<const uint8_t *>(h_scan);
+    int64_t at = PM_SCAN_HEAD + PM_SCAN_LIST_BYTES(c->kind, n) + (n + 7) / 8 * 8;
+    if (frames) at += PM_SCAN_FRAME_TABLE_BYTES(n) + PM_SCAN_FRAME_AREA_BYTES(n);
+    if (packets) at += PM_SCAN_PACKET_TABLE_BYTES(n) + PM_SCAN_PACKET_AREA_BYTES(n);
+    if (!pm_addrs::table_fits(scan + at, n, addr_first))
+        return pm_set_error(PM_ERR_ARG, "pm_codec_decode_addrs: the checkpoint table does not belong to a stream of %lld bytes that begins at address %lld", (long long)n,
+                            (long long)addr_first);
+    pm_addrs::Lookup look{scan + at, h_steps, 0, 0};
+    const pm_addrs::Ref a{&look};
+    const bool ok = frames ? c->feed_framed(h_plain, a, n, scan) : packets ? c->feed_packets(h_plain, a, n, scan) : c->feed_scanned(h_plain, a, n, scan);
+    c->addr_lookups += look.lookups;
+    c->addr_steps += look.nsteps;
+    if (!ok) return pm_set_error(PM_ERR_ARG, "pm_codec_decode_addrs: the lists do not belong to a stream of %lld bytes", (long long)n);
+    c->fresh = false;
+    c->fed += n;
+    *h_pending = (int64_t)c->sink.q.size();
+    return PM_OK;
+}
+
+int pm_codec_addr_work(pm_codec *c, int64_t *h_lookups, int64_t *h_steps)
+{
+    if (!c) return pm_set_error(PM_ERR_ARG, "pm_codec_addr_work: no codec");
+    if (h_lookups) *h_lookups = c->addr_lookups;
+    if (h_steps) *h_steps = c->addr_steps;
+    return PM_OK;
+}
+
 int pm_codec_walked(pm_codec *c, int64_t *h_walked, int64_t *h_jumped)
 {
     if (!c) return pm_set_error(PM_ERR_ARG, "pm_codec_walked: no codec");
@@ -1254,6 +1314,14 @@ int pm_host_decode_batch(pm_host_job *jobs, int njobs, int threads)
         thread_local std::vector<int64_t> wide;
         if (!q.h_plain && !q.h_scan && (int64_t)plain.size() < q.n) plain.resize((size_t)q.n);
         const int64_t *addr = q.h_addr;
+        if (!addr && q.h_scan && q.scan_addrs) {             // the block has checkpoints: an address is resolved where a decoder asks for one
+            const uint8_t *scan = static_cast<const uint8_t *>(q.h_scan);
+            const uint8_t *bytes = scan + PM_SCAN_HEAD + PM_SCAN_LIST_BYTES(q.codec->kind, q.n);
+            if (q.h_plain && q.n > 0) memcpy(q.h_plain, bytes, (size_t)q.n);
+            memcpy(&q.lfsr_state, scan, 8);
+            q.status = pm_codec_decode_addrs(q.codec, bytes, q.h_addr_delta, q.addr_first, q.n, scan, q.scan_frames, q.scan_packets, &q.pending);
+            return;
+        }
         if (!addr && q.n > 0) {                 // the compact form of pm_slice_compact: first address + 16-bit steps
             if ((int64_t)wide.size() < q.n) wide.resize((size_t)q.n);
             int64_t a = q.addr_first;

@@ -53,6 +53,7 @@ struct pm_tuning {
     int bitscan_packet_waves = 0;      // PM_BITSCAN_PACKET_WAVES: waves per job of pm_stream_scan's blocks launch, 1 .. 1024 (0: the default, 64)
     int pipe_packets = 0;              // PM_PIPE_PACKETS: pipe_scan, and the IL2P chains' attempts (headers and RS blocks) are made on the device too
     int pipe_frames = 0;               // PM_PIPE_FRAMES: pipe_scan, and the AX.25 chains' frames (de-stuffed bytes and CRC) come from the device too
+    int pipe_addrs = 0;                // PM_PIPE_ADDRS: pipe_scan, and the scan jobs write address checkpoints: the host stage resolves an address where a decoder asks for one and expands none
     int sweep_no_tail = 0;             // PM_SWEEP_NO_TAIL: the matrix-pipe sweep sends every uncertain sample to the list (round 4), none to its own workgroup's exact chain
 };
 pm_tuning pm_tuning_from_env();

@@ -145,6 +145,7 @@ struct pm_pipe {
     bool keep_slices = false, trace = false;
     bool packets = false;                // pipe_packets: scan, and the IL2P chains' scan jobs make their attempts (pm_scan_job.packets), which the host stage looks its hits up in
     bool frames = false;                 // pipe_frames: scan, and the AX.25 chains' scan jobs write their frames (pm_scan_job.frames), which the host stage queues as they are
+    bool addrs = false;                  // pipe_addrs: scan, and every scan job writes its address checkpoints (pm_scan_job.addrs), from which the host stage resolves the few addresses it needs
     bool scan = false;                   // pipe_scan of the context the pipeline was made on: pm_stream_scan behind the slicers, the host stage decodes from its lists
     bool host_copy = false;              // PM_PIPE_HOST_COPY: the slicers' compact output through a device block and a copy (round 4), not written to the host block by the kernel
     bool skip_decode = false;            // PM_PIPE_SKIP_DECODE (diagnosis only): the host stage decodes nothing -- what the GPU stages alone sustain
@@ -454,6 +455,7 @@ void slice_worker(pm_pipe *p, int wi)
                 dense_cap += PM_SCAN_HEAD + (size_t)PM_SCAN_LIST_BYTES(p->chains[k % nch].codec_kind, cnt) + ((size_t)cnt + 7) / 8 * 8;
                 if (p->frames && p->chains[k % nch].codec_kind == 0) dense_cap += (size_t)PM_SCAN_FRAME_TABLE_BYTES(cnt) + (size_t)PM_SCAN_FRAME_AREA_BYTES(cnt);
                 if (p->packets && p->chains[k % nch].codec_kind == 1) dense_cap += (size_t)PM_SCAN_PACKET_TABLE_BYTES(cnt) + (size_t)PM_SCAN_PACKET_AREA_BYTES(cnt);
+                if (p->addrs) dense_cap += (size_t)PM_SCAN_ADDR_BYTES(cnt);
             }
             dense_cap += 256 * ((nscan + 63) / 64);
             // The compact kernel writes the batch's output STRAIGHT into a page-locked host block (the device reaches it over the link:
@@ -506,7 +508,7 @@ void slice_worker(pm_pipe *p, int wi)
                     const pm_pipe_chain &ch = p->chains[k % nch];
                     const pm_slice_job &q = jobs[(size_t)jidx[k]];
                     sj[k] = pm_scan_job{q.d_data, q.count, ch.lfsr_poly, 0, ch.lfsr_invert, ch.codec_kind, ch.sync_tol, p->frames && ch.codec_kind == 0 ? 1 : 0,
-                                        p->packets && ch.codec_kind == 1 ? 1 : 0, ch.crc, ch.disable_rs, ch.min_dist};
+                                        p->packets && ch.codec_kind == 1 ? 1 : 0, ch.crc, ch.disable_rs, ch.min_dist, p->addrs ? q.d_addr : nullptr, p->addrs ? 1 : 0};
                 }
                 for (size_t j0 = 0; j0 < nscan && !rc; j0 += 64) {
                     const int nj = (int)std::min<size_t>(64, nscan - j0);
@@ -616,6 +618,7 @@ void host_worker(pm_pipe *p)
                     j.h_scan = r.block->p + r.scan_off[c];
                     j.scan_frames = p->frames && ch.codec_kind == 0;
                     j.scan_packets = p->packets && ch.codec_kind == 1;
+                    j.scan_addrs = p->addrs && !j.h_addr;       // (a recording that fetched its full addresses keeps the pointer form)
                 }
             }
             if (!rc && p->keep_slices) {
@@ -758,7 +761,8 @@ int pm_pipe_create(pm_ctx *ctx, const pm_pipe_desc *desc, pm_pipe **out)
     p->keep_slices = d.keep_slices != 0;
     p->frames = ctx->tune.pipe_frames != 0;
     p->packets = ctx->tune.pipe_packets != 0;
-    p->scan = ctx->tune.pipe_scan != 0 || p->frames || p->packets;
+    p->addrs = ctx->tune.pipe_addrs != 0;
+    p->scan = ctx->tune.pipe_scan != 0 || p->frames || p->packets || p->addrs;
     p->trace = getenv("PM_PIPE_TRACE") != nullptr;
     p->skip_decode = getenv("PM_PIPE_SKIP_DECODE") != nullptr;
     p->host_copy = getenv("PM_PIPE_HOST_COPY") != nullptr;

@@ -270,10 +270,11 @@ class SlicedRun:
             out.append(AddressedArray.from_steps(host[o + sw:o + sw + c], host[o:o + 2 * c].view(np.uint16), int(recs["first_addr"][k])))
         return out
 
-    def fetch_scanned(self, row0, nrows, chains, frames, packets, copy_ctx=None, tag=None):
+    def fetch_scanned(self, row0, nrows, chains, frames, packets, copy_ctx=None, tag=None, addrs=False):
         """fetch() with the bitstream stage on the device in front of the copy (pm_rows_scan): `chains` are the run's chains [name, modem,
         slicer, stream, codec], row k a stream of chain k % len(chains) that starts from that chain's LFSR register; frames / packets: the
-        AX.25 chains' frame tables / the IL2P chains' packet tables too.  -> per row (address steps, first address, n, the row's scan part
+        AX.25 chains' frame tables / the IL2P chains' packet tables too; addrs: every row's address checkpoints at the end of its part
+        (pm_rows_scan_chain.addrs).  -> per row (address steps, first address, n, the row's scan part
         -- record, list, descrambled bytes, tables -- as views of one host block): one scan and ONE copy to the host for the lot."""
         ctx = copy_ctx or self.ctx
         recs = self.records()[row0:row0 + nrows]
@@ -286,8 +287,9 @@ class SlicedRun:
             d.codec_kind, d.sync_tol = int(codec._kind), int(codec.sync_tolerance)
             d.frames, d.packets = int(bool(frames) and codec._kind == 0), int(bool(packets) and codec._kind == 1)
             d.il2p_crc, d.il2p_disable_rs, d.il2p_min_dist = int(codec.collect_trailing_crc), int(codec.disable_rs), int(codec.min_distance)
+            d.addrs = int(bool(addrs))
         of = [desc[(row0 + k) % nchains] for k in range(nrows)]
-        parts = [N.scan_part_bytes(d.codec_kind, d.frames, d.packets, int(c)) for d, c in zip(of, counts)]
+        parts = [N.scan_part_bytes(d.codec_kind, d.frames, d.packets, int(c), d.addrs) for d, c in zip(of, counts)]
         used = int(sum(N.rows_scan_steps_bytes(int(c)) for c in counts) + sum(parts))
         # (the same 8 MB size classes as fetch(): the groups of a run ask for the same class and the page-locked blocks go round)
         room = (used + (8 << 20) - 1) // (8 << 20) * (8 << 20)
@@ -347,7 +349,7 @@ def _scannable(chain_sets):
 
 
 def process_recordings_device(chain_sets, audios, ctx=None, chunk=0, rows=False, chain_ids=None, stages=None, slot=0, defer=False, scan=None,
-                              frames=None, packets=None):
+                              frames=None, packets=None, addrs=None):
     """chain_sets[k] = the chains [name, modem, slicer, stream, codec] of recording k (every recording brings the same group of
     chains, as a service decoding successive recordings with one config does), audios[k] its int16 samples (host array or
     DeviceBuffer; equal lengths).  -> [[packets of chain 0, ...] per recording], identical to chain_execute.process_chain on each
@@ -358,7 +360,9 @@ def process_recordings_device(chain_sets, audios, ctx=None, chunk=0, rows=False,
     scan / frames / packets (None: the context's switches pipe_scan, pipe_frames, pipe_packets, read from PM_PIPE_SCAN / FRAMES / PACKETS when
     it was made; frames and packets imply scan): the bitstream stage of the fused-slicer route runs on the device, a group of rows per
     pm_rows_scan (SlicedRun.fetch_scanned), and the codecs decode from its lists -- with frames the AX.25 chains' frames, with packets the
-    IL2P chains' headers and RS blocks come from there too.  Results are the same; stages["scanned"] says which way the decode went."""
+    IL2P chains' headers and RS blocks come from there too.  addrs (None: the context's switch pipe_addrs, PM_PIPE_ADDRS; implies scan): the
+    rows bring address checkpoints and the codecs resolve an address where they need one instead of expanding every step.  Results are the
+    same; stages["scanned"] says which way the decode went."""
     from .chain_execute import _host_rows, _host_rows_scanned, _host_stages, _host_stages_scanned, _pool
     from .slicer import slice_batch
     ctx = ctx or Context.default()
@@ -367,7 +371,8 @@ def process_recordings_device(chain_sets, audios, ctx=None, chunk=0, rows=False,
         return (lambda: []) if defer else []
     frames = bool(ctx.tuned("pipe_frames")) if frames is None else bool(frames)
     packets = bool(ctx.tuned("pipe_packets")) if packets is None else bool(packets)
-    scan = (bool(ctx.tuned("pipe_scan")) if scan is None else bool(scan)) or frames or packets
+    addrs = bool(ctx.tuned("pipe_addrs")) if addrs is None else bool(addrs)
+    scan = (bool(ctx.tuned("pipe_scan")) if scan is None else bool(scan)) or frames or packets or addrs
     dev = []
     for a in audios:
         if isinstance(a, DeviceBuffer):
@@ -427,13 +432,14 @@ def process_recordings_device(chain_sets, audios, ctx=None, chunk=0, rows=False,
                         hi = min(lo + per, cuts[p + 1])
                         if scanned:
                             # the bitstream stage on the device in front of the copy; a recording's rows go to the codecs at once
-                            got = run.fetch_scanned(lo * nchains, (hi - lo) * nchains, chain_sets[0], frames, packets, sides[p], tag=("loop-sliced", p))
+                            got = run.fetch_scanned(lo * nchains, (hi - lo) * nchains, chain_sets[0], frames, packets, sides[p], tag=("loop-sliced", p),
+                                                    addrs=addrs)
                             for rec in range(lo, hi):
                                 mine = got[(rec - lo) * nchains:(rec - lo + 1) * nchains]
                                 if rows:
-                                    early[rec] = _pool().submit(_host_rows_scanned, chain_sets[rec], mine, chain_ids, frames, packets)
+                                    early[rec] = _pool().submit(_host_rows_scanned, chain_sets[rec], mine, chain_ids, frames, packets, addrs)
                                 else:
-                                    early[rec] = _pool().submit(_host_stages_scanned, chain_sets[rec], mine, frames, packets)
+                                    early[rec] = _pool().submit(_host_stages_scanned, chain_sets[rec], mine, frames, packets, addrs)
                             if stages is not None:          # (diagnosis only: the slicers' bytes as the old way brings them)
                                 out += run.fetch(lo * nchains, (hi - lo) * nchains, sides[p], tag=("loop-sliced", p))
                             continue

@@ -3,8 +3,8 @@
 jobs write their frames too (pm_scan_job.frames), and two thirds of their streams are frames of 60-250 bytes between single flags, as
 the headline's streams are, instead of random bytes (whose frames are the few short ones that chance makes).  --packets: the IL2P jobs make
 their attempts too (pm_scan_job.packets), on streams with a packet of 20-250 payload bytes every 400 bytes or so, as fsk_9600's dense
-recordings have them.
-    rocprofv3 --kernel-trace --stats -d <dir> -- python tools/scan_probe.py [reps] [--frames] [--packets]"""
+recordings have them.  --addrs: every job writes its address checkpoints too (pm_scan_job.addrs), from addresses eight symbol periods apart.
+    rocprofv3 --kernel-trace --stats -d <dir> -- python tools/scan_probe.py [reps] [--frames] [--packets] [--addrs]"""
 import ctypes
 import os
 import sys
@@ -15,8 +15,8 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import pymodem_amd                                                    # noqa: E402
 from pymodem_amd import siggen                                        # noqa: E402
-from pymodem_amd._native import (SCAN_HEAD, ScanJob, check, lib, scan_frame_area_bytes, scan_frame_table_bytes, scan_list_bytes,      # noqa: E402
-                                 scan_packet_area_bytes, scan_packet_table_bytes)
+from pymodem_amd._native import (SCAN_HEAD, ScanJob, check, lib, scan_addr_bytes, scan_frame_area_bytes, scan_frame_table_bytes,      # noqa: E402
+                                 scan_list_bytes, scan_packet_area_bytes, scan_packet_table_bytes)
 
 
 def framed_stream(rng, n, poly):
@@ -46,6 +46,7 @@ def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     frames = "--frames" in sys.argv[1:]
     packets = "--packets" in sys.argv[1:]
+    addrs = "--addrs" in sys.argv[1:]
     reps = int(args[0]) if args else 50
     ctx = pymodem_amd.Context.default()
     n = 450_000
@@ -55,6 +56,7 @@ def main():
     dense = {inv: packet_stream(rng, n, inv) for inv in (0, 1)} if packets else None
     bufs = [ctx.upload(framed if frames and chains[k % len(chains)][2] == 0 else dense[chains[k % len(chains)][1]] if packets and chains[k % len(chains)][2] == 1
                        else rng.integers(0, 256, n, dtype=np.uint8)) for k in range(4 * len(chains))]
+    d_addr = ctx.upload(1000 + 40 * np.arange(n, dtype=np.int64)) if addrs else None
     jobs = (ScanJob * len(bufs))()
     need = 0
     for k, (q, b) in enumerate(zip(jobs, bufs)):
@@ -64,6 +66,9 @@ def main():
         q.packets, q.il2p_crc = int(packets and kind == 1), 1
         need += SCAN_HEAD + scan_list_bytes(kind, n) + (n + 7) // 8 * 8 + (scan_frame_table_bytes(n) + scan_frame_area_bytes(n) if q.frames else 0)
         need += scan_packet_table_bytes(n) + scan_packet_area_bytes(n) if q.packets else 0
+        if addrs:
+            q.d_addr, q.addrs = d_addr.ptr.value, 1
+            need += scan_addr_bytes(n)
     block = ctx.empty(need, np.uint8)
     offs, used = (ctypes.c_int64 * len(bufs))(), ctypes.c_size_t()
     for timed in (False, True):
@@ -74,7 +79,7 @@ def main():
         ctx.sync()
         if timed:
             ms = (time.perf_counter() - t0) * 1e3 / reps
-            print(f"pm_stream_scan{' with frames' if frames else ''}{' with packets' if packets else ''}: {len(bufs)} streams x {n} bytes, {ms:.3f} ms per call (host clock around {reps} calls and a stream wait), "
+            print(f"pm_stream_scan{' with frames' if frames else ''}{' with packets' if packets else ''}{' with addrs' if addrs else ''}: {len(bufs)} streams x {n} bytes, {ms:.3f} ms per call (host clock around {reps} calls and a stream wait), "
                   f"{len(bufs) * n / ms / 1e6:.1f} GB/s of slicer bytes")
 
 
