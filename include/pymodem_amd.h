@@ -452,8 +452,44 @@ typedef struct pm_scan_job {
     int32_t il2p_crc, il2p_disable_rs, il2p_min_dist;      /* ... for a codec with these options (pm_codec_create) */
     const int64_t *d_addr;           /* with addrs: the stream addresses of the n bytes, on the device */
     int32_t addrs;                   /* 1 (any kind): the address checkpoints behind everything else of the part */
+    struct pm_scan_carry *d_carry;   /* NULL, or the stream's carry (below): the job is the next PIECE of a stream; lfsr_state is ignored */
 } pm_scan_job;
 int pm_stream_scan(pm_ctx *ctx, const pm_scan_job *h_jobs, int njobs, void *d_block, size_t block_bytes, int64_t *h_offsets, size_t *h_used);
+/* A stream scanned in PIECES: what one piece hands to the next, in device memory, owned by the caller, one per stream (8-byte aligned).  A job
+ * with d_carry starts from it instead of from a just-created decoder's state -- word 0's LFSR term is `lfsr_state`, the bits in front of
+ * word 0 are `tail`, the bits counted since the last reset are `counted` -- and leaves it as the stream stands behind the piece, so that
+ * the records, lists, frames and packets of the pieces are what a decoder that is fed the pieces one after the other has to do.  The pieces
+ * of a stream go in stream order through calls on the same context's stream; nothing waits for the host in between.  Two jobs of one call
+ * that name the same carry are PM_ERR_ARG.
+ *   state   START: nothing scanned yet, the decoder is just created.  OK: `ones` and `counted` are the decoder's.  LOST: the piece before
+ *           bailed (or the carry was seeded so): the decoder's counters are not known, the first reset of the next piece is its bail bit and
+ *           the host takes that piece through its table; pm_scan_carry_set from the codec's registers (pm_codec_scan_state) makes it OK again.
+ *   counted behind the piece's last reset: 8 n - (last reset + 1) - the stuffed zeros dropped behind it; without a reset in the piece what
+ *           it was plus 8 n - the piece's dropped zeros -- wherever a bail fell.  AX.25 jobs only (others leave it as it is).
+ * What differs from a job without a carry in a piece that does not start in START: the stream's first listed flag (F none) may close a
+ * frame that began in an earlier piece, whose bytes the device does not have: with `frames` its table entry is {len -1, crc 0}, "not made",
+ * and the host takes the bytes up to that flag through its registers.  An IL2P attempt that runs past the piece's end is INCOMPLETE.
+ * A part made with a carry ends with one more piece, the CARRY PIECE, PM_SCAN_CARRY_BYTES behind everything else (behind the address
+ * checkpoints when those are on): what the job started from,
+ *       int32 state, int32 ones, int64 counted, int64 pieces, int64 bytes
+ * for the host to hold its codec against (pm_codec_decode_carried).  Everything in front of it lies where it lies without a carry, and for a
+ * START carry is byte for byte the same. */
+#define PM_SCAN_CARRY_START 0
+#define PM_SCAN_CARRY_OK 1
+#define PM_SCAN_CARRY_LOST 2
+#define PM_SCAN_CARRY_BYTES 32
+typedef struct pm_scan_carry {
+    uint64_t lfsr_state;             /* the LFSR's register behind the last piece */
+    uint64_t tail;                   /* the last 64 descrambled bits (after invert) in stream order: bit 63 is the stream's last bit */
+    int64_t counted;                 /* bits appended since the last reset, stuffed zeros left out: the decoder's nbytes * 8 + nbits */
+    int64_t pieces, bytes;           /* pieces and bytes taken so far */
+    int32_t ones;                    /* the run of ones that ends the stream so far, capped at 7 */
+    int32_t state;                   /* PM_SCAN_CARRY_START / _OK / _LOST */
+} pm_scan_carry;
+/* Seed a carry, enqueued on the ctx stream: (reg, 0, 0) starts a stream -- state START, for a just-created codec; other values seed OK from a
+ * decoder that has been fed (ones, counted: pm_codec_scan_state), with `ones` ones behind a zero as the tail; counted < 0 seeds LOST.
+ * pieces and bytes start at 0. */
+int pm_scan_carry_set(pm_ctx *ctx, pm_scan_carry *d_carry, uint64_t lfsr_state, int32_t ones, int64_t counted);
 /* How many chunks (= walkers) a batch is cut into on this ctx, within 1024..16384 samples per chunk; 0 restores the default 16384.
  * Lane-steps are N (1 + m/L) for merge length m (10-20 k samples) and chunk length L, the depth is (L + longest merge) x the
  * step time: long chunks are cheap, short ones are quick.  Results do not depend on it. */
@@ -662,6 +698,22 @@ int pm_codec_decode_packets(pm_codec *c, const uint8_t *h_plain, const int64_t *
  * cannot belong to the stream: A[0] != addr_first, a place below the one in front of it, or more than 64 * 65535 above it. */
 int pm_codec_decode_addrs(pm_codec *c, const uint8_t *h_plain, const uint16_t *h_steps, int64_t addr_first, int64_t n, const void *h_scan, int32_t frames,
                           int32_t packets, int64_t *h_pending);
+/* The scanned routes for a part made with pm_scan_job.d_carry, for a codec in ANY state: the next piece of a stream that is scanned in
+ * pieces.  frames, packets, addrs: how the part was made; the addresses come as h_addr (n of them), or, with h_addr NULL, as h_steps and
+ * addr_first (with addrs they are resolved from the checkpoints as in pm_codec_decode_addrs, without addrs they are expanded).  The part
+ * ends with the carry piece, which must agree with the codec: for an AX.25 codec state START goes with a codec that has never been fed and
+ * state OK with one whose `ones` and `counted` (pm_codec_scan_state) are the carry piece's -- compared only while both counts are below
+ * 8000 bits; state LOST goes with any.  (An IL2P codec's attempts depend on nothing in front of the piece: only the piece number counts.)
+ * The piece number must be the next one for this codec: 0 (a carry just seeded) or one more than the last piece taken.  A disagreement is
+ * PM_ERR_ARG with the codec untouched.  Piece 0 is taken at any time, because a carry may be seeded at any time: a REPLAYED first piece is
+ * refused only where the state gives it away (an AX.25 codec that has been fed, with a START piece; registers that have moved on from an OK
+ * piece's).  An IL2P codec cannot tell a replayed piece 0 from a new seed and decodes it again: feeding each part once is the caller's.  The routes are the three above: from byte 0 to the first listed flag the AX.25 decoder runs on its
+ * own registers, and a "not made" first entry of the frame table does the same; the IL2P search starts in whatever state the codec is in. */
+int pm_codec_decode_carried(pm_codec *c, const uint8_t *h_plain, const int64_t *h_addr, const uint16_t *h_steps, int64_t addr_first, int64_t n,
+                            const void *h_scan, int32_t frames, int32_t packets, int32_t addrs, int64_t *h_pending);
+/* The AX.25 decoder's two registers that a carry is seeded from (pm_scan_carry_set): the run of ones that ends what it has been fed, capped
+ * at 7, and the bits counted since the last reset (nbytes * 8 + nbits).  An IL2P codec gives 0, 0. */
+int pm_codec_scan_state(pm_codec *c, int32_t *h_ones, int64_t *h_counted);
 /* Addresses this codec has resolved from a checkpoint so far, and the 16-bit steps it added for them (either may be NULL): at most 63 steps
  * per look-up, and a look-up per queued packet or walked byte at the most. */
 int pm_codec_addr_work(pm_codec *c, int64_t *h_lookups, int64_t *h_steps);
@@ -694,6 +746,7 @@ typedef struct pm_host_job {
     int32_t scan_packets;         /* with h_scan, IL2P codecs only: the block was made with pm_scan_job.packets -> pm_codec_decode_packets */
     int32_t scan_addrs;           /* with h_scan, h_addr == NULL and h_addr_delta: the block was made with pm_scan_job.addrs -> the same route */
                                   /* through pm_codec_decode_addrs: no address is expanded, each comes from its checkpoint where it is asked for */
+    int32_t scan_carry;           /* with h_scan: the block was made with pm_scan_job.d_carry -> pm_codec_decode_carried, for a codec in any state */
 } pm_host_job;
 int pm_host_decode_batch(pm_host_job *jobs, int njobs, int threads);
 int pm_codec_fetch_batch(pm_codec *const *codecs, const int64_t *counts, int n, pm_packet *h_out, int threads);

@@ -86,7 +86,7 @@ class HostJob(ctypes.Structure):
                 ("lfsr_invert", ctypes.c_int32), ("status", ctypes.c_int32),
                 ("h_addr_delta", ctypes.c_void_p), ("addr_first", ctypes.c_int64), ("h_plain", ctypes.c_void_p),
                 ("h_scan", ctypes.c_void_p), ("scan_frames", ctypes.c_int32), ("scan_packets", ctypes.c_int32),
-                ("scan_addrs", ctypes.c_int32)]
+                ("scan_addrs", ctypes.c_int32), ("scan_carry", ctypes.c_int32)]
 
 
 class ScanJob(ctypes.Structure):
@@ -94,7 +94,29 @@ class ScanJob(ctypes.Structure):
     _fields_ = [("d_data", ctypes.c_void_p), ("n", ctypes.c_int64), ("lfsr_poly", ctypes.c_uint64), ("lfsr_state", ctypes.c_uint64),
                 ("lfsr_invert", ctypes.c_int32), ("codec_kind", ctypes.c_int32), ("sync_tol", ctypes.c_int32), ("frames", ctypes.c_int32),
                 ("packets", ctypes.c_int32), ("il2p_crc", ctypes.c_int32), ("il2p_disable_rs", ctypes.c_int32), ("il2p_min_dist", ctypes.c_int32),
-                ("d_addr", ctypes.c_void_p), ("addrs", ctypes.c_int32)]
+                ("d_addr", ctypes.c_void_p), ("addrs", ctypes.c_int32), ("d_carry", ctypes.c_void_p)]
+
+
+class ScanCarry(ctypes.Structure):
+    """pm_scan_carry"""
+    _fields_ = [("lfsr_state", ctypes.c_uint64), ("tail", ctypes.c_uint64), ("counted", ctypes.c_int64), ("pieces", ctypes.c_int64),
+                ("bytes", ctypes.c_int64), ("ones", ctypes.c_int32), ("state", ctypes.c_int32)]
+
+
+SCAN_CARRY_START, SCAN_CARRY_OK, SCAN_CARRY_LOST = 0, 1, 2      # PM_SCAN_CARRY_START / _OK / _LOST
+SCAN_CARRY_BYTES = 32                                           # PM_SCAN_CARRY_BYTES
+
+
+def scan_carry_dtype():
+    """NumPy view of a pm_scan_carry."""
+    import numpy as np
+    return np.dtype([("lfsr_state", "<u8"), ("tail", "<u8"), ("counted", "<i8"), ("pieces", "<i8"), ("bytes", "<i8"), ("ones", "<i4"), ("state", "<i4")])
+
+
+def scan_carry_piece_dtype():
+    """NumPy view of the carry piece that ends a part made with pm_scan_job.d_carry: what the job started from."""
+    import numpy as np
+    return np.dtype([("state", "<i4"), ("ones", "<i4"), ("counted", "<i8"), ("pieces", "<i8"), ("bytes", "<i8")])
 
 
 class RowsScanChain(ctypes.Structure):
@@ -375,6 +397,9 @@ _SIGS = {
     "pm_codec_decode_framed": ([_vp, _vp, _vp, _i64, _vp, ctypes.POINTER(_i64)], _int),
     "pm_codec_decode_packets": ([_vp, _vp, _vp, _i64, _vp, ctypes.POINTER(_i64)], _int),
     "pm_codec_walked": ([_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)], _int),
+    "pm_scan_carry_set": ([_vp, _vp, ctypes.c_uint64, ctypes.c_int32, _i64], _int),
+    "pm_codec_decode_carried": ([_vp, _vp, _vp, _vp, _i64, _i64, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_i64)], _int),
+    "pm_codec_scan_state": ([_vp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_i64)], _int),
     "pm_codec_decode_addrs": ([_vp, _vp, _vp, _i64, _i64, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(_i64)], _int),
     "pm_codec_addr_work": ([_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)], _int),
     "pm_codec_fetch": ([_vp, _vp, _i64, ctypes.POINTER(_i64)], _int),

@@ -23,6 +23,10 @@
 // bytes.  The job form has the slicer's full addresses on the device: the tile launch's lane of every eighth word stores its byte's.  The
 // row form has 16-bit steps: the tile launch leaves each tile's sum of steps with its summary, the combine launch's wave carries an int64
 // prefix from tile to tile, and a small launch of its own scans the lanes of every tile and stores (rows_addrs_kernel).
+// With pm_scan_job.d_carry a job is the next PIECE of a stream (pm_scan_carry, in device memory): word 0's LFSR term and the bits in front
+// of it come from the carry, the combine launch starts from the carry's counted bits instead of from a just-created decoder's state, and
+// its lane 0 echoes the carry-in into the carry piece at the part's end and into scratch, then writes the carry-out.  The launches behind
+// it read the scratch copy, never d_carry, so the pieces of a stream follow each other on the stream without the host in between.
 #include "pm_common.h"
 #include "pm_bitscan_addrs.h"
 #include "pm_bitscan_events.h"
@@ -51,6 +55,9 @@ struct Job {
     bool ok;                                // false: the job is left out, nothing is stored for it (rows only)
     const int64_t *addr;                    // the job form's addrs: the n stream addresses, nullptr: no checkpoints
     bool ckpt;                              // the row form's addrs: checkpoints from the row's steps
+    uint64_t tail;                          // the descrambled bits in front of word 0 (a just-created decoder: zeros)
+    pm_scan_carry *carry;                   // the piece's carry (pm_scan_job.d_carry), nullptr: none.  Read by the tile and combine launches only
+    bool started;                           // a piece whose carry is not START: its first listed flag's frame is not made
 };
 
 struct ScanJobs {
@@ -65,7 +72,12 @@ struct ScanJobs {
     int32_t frame_words;
     int32_t pk0[kScanJobs];                 // packets: the job's first place in the device-side candidate list, records and work list, -1: no packets
     uint8_t pkopt[kScanJobs];               // packets: the codec's crc | disable_rs << 1 | min_dist (0 .. 9) << 2
+    int8_t carried[kScanJobs];              // 1: reg0 holds pm_scan_job.d_carry instead of a register
     const int64_t *addr[kScanJobs];         // addrs: the job's stream addresses, nullptr: no checkpoints
+    // The carries as the jobs found them, copied to scratch by the combine launch before it writes the carry-out: the launches behind it
+    // (late = 1) take register, tail and state from there, the tile and combine launches (late = 0) from d_carry itself.
+    const pm_scan_carry *carry_in;
+    int32_t late;
 
     __device__ int tiles() const { return tile0[njobs]; }
     __device__ int job_of_tile(int tile) const
@@ -76,8 +88,16 @@ struct ScanJobs {
     }
     __device__ Job job(int j) const
     {
-        return Job{data[j], poly[j], reg0[j], off[j], ev0[j], pk0[j], n[j], tile0[j], tile0[j + 1], kind[j], invert[j], tol[j], pkopt[j], true,
-                   addr[j], false};
+        Job jb{data[j], poly[j], reg0[j], off[j], ev0[j], pk0[j], n[j], tile0[j], tile0[j + 1], kind[j], invert[j], tol[j], pkopt[j], true,
+               addr[j], false, 0, nullptr, false};
+        if (carried[j]) {
+            jb.carry = reinterpret_cast<pm_scan_carry *>(reg0[j]);
+            const pm_scan_carry *c = late ? carry_in + j : jb.carry;
+            jb.reg0 = c->lfsr_state;
+            jb.tail = c->tail;
+            jb.started = c->state != PM_SCAN_CARRY_START;
+        }
+        return jb;
     }
     __device__ void copy_steps(uint8_t *, const Job &, int, int64_t) const {}      // (the job form's block has no steps)
     __device__ void load_steps(int, int64_t, uint64_t *, uint64_t *) const {}
@@ -109,7 +129,7 @@ struct RowJobs {
         const pm_rows::Entry e = table[j];
         const int c = (int)((row0 + j) % nchains);
         return Job{data + (row0 + j) * cap, poly[c], reg0[c], e.off + pm_rows::steps_bytes(e.n), e.ev0, e.pk0, e.n, e.tile0, table[j + 1].tile0,
-                   kind[c], invert[c], tol[c], pkopt[c], e.off >= 0, nullptr, addrs[c] != 0};
+                   kind[c], invert[c], tol[c], pkopt[c], e.off >= 0, nullptr, addrs[c] != 0, 0, nullptr, false};
     }
     // the eight steps of data word w of row j (8 w < n <= cap, and cap is a multiple of 8: they lie inside the row)
     __device__ void load_steps(int j, int64_t w, uint64_t *lo, uint64_t *hi) const
@@ -136,6 +156,7 @@ constexpr int kPacketWaves = 64;            // waves that share a job's placed r
 constexpr int kRowFrameWaves = 16;          // the same for a row of pm_rows_scan: thousands of rows of tens to hundreds of KB each
 constexpr int kRowPacketWaves = 8;
 constexpr uint32_t kClosesNothing = 0xFFFFFFFEu;   // F of the stream's first flag in the device-side copy when no frame ends there
+constexpr uint32_t kNotMade = 0xFFFFFFFDu;         // F of a later piece's first listed flag there: what it closes began in an earlier piece
 
 __device__ inline uint64_t load_word(const uint8_t *d, int64_t n, int64_t w)
 {
@@ -270,7 +291,7 @@ __global__ __launch_bounds__(kLanes) void bitscan_tile_kernel(Jobs J, uint8_t *b
         const uint64_t i0 = load_word(d, n, w), i1 = load_word(d, n, w - 1), i2 = load_word(d, n, w - 2);
         valid = valid_bits(n, w);
         x = plain_word(jb, w, i0, i1) & valid;
-        xp = w ? plain_word(jb, w - 1, i1, i2) : 0;           // (a fresh decoder: zeros in front of the stream)
+        xp = w ? plain_word(jb, w - 1, i1, i2) : jb.tail;     // (a fresh decoder: zeros in front of the stream; a later piece: the carry's tail)
         *reinterpret_cast<uint64_t *>(plain + 8 * w) = __builtin_bswap64(__brevll(x));       // the bytes are padded to 8: the last store is whole
         J.copy_steps(block, jb, j, w);
         // the job form's checkpoints: byte 8 w is byte 64 (w / 8) and 8 w < n, so the place is one of the table's (n + 63) / 64
@@ -323,14 +344,22 @@ __global__ __launch_bounds__(kLanes) void bitscan_tile_kernel(Jobs J, uint8_t *b
 // Launch 2: a wave per stream takes the summaries in order, 64 at a time (a lane loads one, all lanes step through them together).
 template <class Jobs>
 __global__ __launch_bounds__(64) void bitscan_combine_kernel(Jobs J, uint8_t *block, const TileSum *sums, TileCarry *carries, int32_t *counts,
-                                                             int64_t *steps_before)
+                                                             int64_t *steps_before, pm_scan_carry *carry_copy)
 {
     const int j = blockIdx.x, lane = threadIdx.x, tw = J.tile_words;
     const Job jb = J.job(j);
     if (!jb.ok) return;
     const int t0 = jb.tile0, nt = jb.tile_end - t0;
     const int kind = jb.kind;
-    Combine st = combine_start();
+    // a piece of a stream starts from its carry: this wave reads it here and, whole, at the end, where its lane 0 writes it
+    int32_t cstate = kCarryStart;
+    int64_t ccounted = 0;
+    if (jb.carry) {
+        cstate = jb.carry->state;
+        ccounted = jb.carry->counted;
+    }
+    Combine st = jb.carry && kind == 0 ? combine_start_carried(cstate, ccounted) : combine_start();
+    PieceEnd pe = piece_end_start(ccounted);
     int32_t cands = 0;
     const bool ckpt = steps_before && jb.ckpt;              // the row form's addrs: the steps of the tiles in front of each tile, in 64 bits
     int64_t steps = 0;
@@ -342,6 +371,7 @@ __global__ __launch_bounds__(64) void bitscan_combine_kernel(Jobs J, uint8_t *bl
             const TileSum of{__shfl(s.dropped, l), __shfl(s.first_reset, l), __shfl(s.dropped_to_first, l), __shfl(s.last_reset, l), __shfl(s.dropped_after_last, l),
                              __shfl(s.first_flag, l), __shfl(s.last_flag, l), __shfl(s.closing, l), __shfl(s.bail, l), __shfl(s.bits, l), 0, 0};
             TileCarry c = kind == 0 ? combine_step(st, of, (int64_t)(r0 + l) * tw * 64) : combine_carry(st);
+            piece_end_step(pe, of, (int64_t)(r0 + l) * tw * 64);
             if (kind == 1) c.events = cands;                // an IL2P tile: the candidates in front of it
             cands += of.closing;
             if (l == lane) mine = c;
@@ -370,6 +400,29 @@ __global__ __launch_bounds__(64) void bitscan_combine_kernel(Jobs J, uint8_t *bl
         *reinterpret_cast<int32_t *>(rec + 24) = kind == 0 ? r.events : 0;
         *reinterpret_cast<int32_t *>(rec + 28) = kind == 1 ? cands : 0;
         if (counts) counts[j] = kind == 0 ? r.events : kind == 1 ? cands : 0;      // for the frames and packets launches: the block may be host memory, nothing is read back from it
+        if (jb.carry) {
+            // the carry-in into the carry piece, behind everything else of the part, and into scratch for the launches behind this one;
+            // then the carry-out.  This lane is d_carry's only writer, and the tile launch has finished.
+            const pm_scan_carry cin = *jb.carry;
+            int64_t *piece = reinterpret_cast<int64_t *>(rec + pm_rows::scan_bytes(kind, jb.ev0 >= 0, jb.pk0 >= 0, n, jb.addr != nullptr));
+            piece[0] = (int64_t)(((uint64_t)(uint32_t)cin.ones << 32) | (uint32_t)cin.state);
+            piece[1] = cin.counted;
+            piece[2] = cin.pieces;
+            piece[3] = cin.bytes;
+            carry_copy[j] = cin;
+            uint64_t last = 0;
+            if (n >= 8) last = stream_bits64(jb, n, 8 * n - 64);
+            else if (n > 0) last = stream_word(jb, n, 0) & valid_bits(n, 0);
+            pm_scan_carry out = cin;
+            out.lfsr_state = reg;
+            out.tail = tail_join(cin.tail, last, n);
+            out.ones = tail_ones(out.tail);
+            if (kind == 0) out.counted = piece_counted(pe, n, out.ones);
+            out.state = piece_state(cin.state, st);
+            out.pieces = cin.pieces + 1;
+            out.bytes = cin.bytes + n;
+            *jb.carry = out;
+        }
     }
 }
 
@@ -390,7 +443,7 @@ __global__ __launch_bounds__(kLanes) void bitscan_emit_kernel(Jobs J, uint8_t *b
         if ((int)threadIdx.x < tw && w < nw) {
             const uint8_t *d = jb.data;
             const uint64_t i0 = load_word(d, n, w), i1 = load_word(d, n, w - 1), i2 = load_word(d, n, w - 2);
-            const uint64_t C = __brevll(plain_word(jb, w, i0, i1) & valid_bits(n, w)), P = __brevll(w ? plain_word(jb, w - 1, i1, i2) : 0);
+            const uint64_t C = __brevll(plain_word(jb, w, i0, i1) & valid_bits(n, w)), P = __brevll(w ? plain_word(jb, w - 1, i1, i2) : jb.tail);
             for (int b = 0; b < 8; ++b) {
                 const int64_t k = 8 * w + b;
                 if (k < 4 || k >= n) continue;
@@ -421,7 +474,7 @@ __global__ __launch_bounds__(kLanes) void bitscan_emit_kernel(Jobs J, uint8_t *b
         const uint64_t i0 = load_word(d, n, w), i1 = load_word(d, n, w - 1), i2 = load_word(d, n, w - 2);
         valid = valid_bits(n, w);
         x = plain_word(jb, w, i0, i1) & valid;
-        xp = w ? plain_word(jb, w - 1, i1, i2) : 0;
+        xp = w ? plain_word(jb, w - 1, i1, i2) : jb.tail;
     }
     Seg total;
     const LaneIn in = lane_prepare(ax25_marks(x, xp, valid), active, lds, &total);
@@ -436,7 +489,8 @@ __global__ __launch_bounds__(kLanes) void bitscan_emit_kernel(Jobs J, uint8_t *b
         if (at + k < cap) events[at + k] = make_uint2(listed_P(l, k), listed_F(l, k));
     if (jb.ev0 >= 0)
         for (int k = 0; k < nfound; ++k)
-            if (at + k < cap) copies[jb.ev0 + at + k] = make_uint2(listed_P(l, k), (l.nothing >> k) & 1 ? kClosesNothing : listed_F(l, k));
+            if (at + k < cap)
+                copies[jb.ev0 + at + k] = make_uint2(listed_P(l, k), jb.started && listed_F(l, k) == 0xFFFFFFFFu ? kNotMade : (l.nothing >> k) & 1 ? kClosesNothing : listed_F(l, k));
 }
 
 // Launch 4 (pm_scan_job.frames): a wave per listed flag {P, F} -- the events e, e + waves, ... of its job, the count read from the combine
@@ -470,6 +524,10 @@ __global__ __launch_bounds__(64) void bitscan_frames_kernel(Jobs J, uint8_t *blo
     auto or_word = [&](int at, uint32_t v) { atomicOr(&line[at], v); };
     for (int32_t e = (int32_t)blockIdx.x; e < count; e += (int32_t)gridDim.x) {
         const uint2 pf = copies[jb.ev0 + e];
+        if (pf.y == kNotMade) {                             // the frame began in an earlier piece: the host's registers have it
+            if (lane == 0) *reinterpret_cast<uint2 *>(table + 8 * (int64_t)e) = make_uint2(0xFFFFFFFFu, 0u);
+            continue;
+        }
         const int64_t P = pf.x, s = pf.y >= kClosesNothing ? 0 : (int64_t)pf.y;
         if (pf.y == kClosesNothing || P >= 8 * n || s >= P) {
             if (lane == 0) *reinterpret_cast<uint2 *>(table + 8 * (int64_t)e) = make_uint2(0u, 0u);
@@ -488,7 +546,7 @@ __global__ __launch_bounds__(64) void bitscan_frames_kernel(Jobs J, uint8_t *blo
             if (active) {
                 const uint64_t i0 = load_word(d, n, w), i1 = load_word(d, n, w - 1), i2 = load_word(d, n, w - 2);
                 x = plain_word(jb, w, i0, i1);
-                const uint64_t xp = w ? plain_word(jb, w - 1, i1, i2) : 0;
+                const uint64_t xp = w ? plain_word(jb, w - 1, i1, i2) : jb.tail;
                 const uint64_t span = low_mask(w == w_last ? (int)((P - 1) & 63) + 1 : 64) & ~low_mask(w == w_first ? (int)(s & 63) : 0);
                 k = word_marks(x, xp, span);
             }
@@ -814,8 +872,10 @@ struct ScanScratch {
     PkRec *recs;
     uint8_t *extra;                         // `extra_bytes` behind everything, 64-byte aligned (the row table)
     int64_t *steps_before;                  // the row form's addrs: per tile the steps of its row's tiles in front, nullptr: no checkpoints
+    pm_scan_carry *carry_in;                // the job form's carries as the jobs found them (kScanJobs of them), nullptr: the row form
 };
-int scan_scratch(pm_ctx *ctx, size_t jobs, int64_t tiles, int64_t copies, int64_t places, size_t extra_bytes, ScanScratch *out, bool steps_before = false)
+int scan_scratch(pm_ctx *ctx, size_t jobs, int64_t tiles, int64_t copies, int64_t places, size_t extra_bytes, ScanScratch *out, bool steps_before = false,
+                 bool carries = false)
 {
     const size_t sums_bytes = ((size_t)tiles * sizeof(TileSum) + 63) & ~(size_t)63;
     // (frames: the event counts and a copy of the lists stay on the device for the frames launch, behind the carries)
@@ -824,7 +884,8 @@ int scan_scratch(pm_ctx *ctx, size_t jobs, int64_t tiles, int64_t copies, int64_
     const size_t lists_bytes = (size_t)copies * sizeof(uint2), cands_bytes = ((size_t)places * sizeof(uint32_t) + 63) & ~(size_t)63, recs_bytes = (size_t)places * sizeof(PkRec);
     const size_t pk_bytes = places ? 2 * cands_bytes + recs_bytes + 2 * jobs * sizeof(int32_t) : 0;
     const size_t extra_padded = (extra_bytes + 63) & ~(size_t)63, before_bytes = steps_before ? (size_t)tiles * sizeof(int64_t) : 0;
-    if (int rc = pm_scratch_reserve(ctx, sums_bytes + carries_bytes + counts_bytes + lists_bytes + pk_bytes + extra_padded + before_bytes + 256)) return rc;
+    const size_t carry_bytes = carries ? kScanJobs * sizeof(pm_scan_carry) : 0;
+    if (int rc = pm_scratch_reserve(ctx, sums_bytes + carries_bytes + counts_bytes + lists_bytes + pk_bytes + extra_padded + before_bytes + carry_bytes + 256)) return rc;
     uint8_t *base = static_cast<uint8_t *>(ctx->d_scratch);
     out->sums = reinterpret_cast<TileSum *>(base);
     out->carries = reinterpret_cast<TileCarry *>(base + sums_bytes);
@@ -837,27 +898,48 @@ int scan_scratch(pm_ctx *ctx, size_t jobs, int64_t tiles, int64_t copies, int64_
     out->recs = reinterpret_cast<PkRec *>(pk + 2 * cands_bytes + 2 * jobs * sizeof(int32_t));
     out->extra = reinterpret_cast<uint8_t *>(((uintptr_t)pk + pk_bytes + 63) & ~(uintptr_t)63);
     out->steps_before = steps_before ? reinterpret_cast<int64_t *>(out->extra + extra_padded) : nullptr;
+    out->carry_in = carries ? reinterpret_cast<pm_scan_carry *>(out->extra + extra_padded + before_bytes) : nullptr;     // (64-byte aligned: extra is, and the others are multiples of 64 or 8)
     return PM_OK;
 }
 
 // the launches behind either table: `emit`: some job has a list to write; frame_waves, packet_waves: the waves that share a job
+// (L: the table for the launches behind the combine -- the job form's with `late` set, see ScanJobs::carry_in)
 template <class Jobs>
-void scan_launch(pm_ctx *ctx, const Jobs &J, int njobs, int64_t tiles, int64_t copies, int64_t places, bool emit, uint8_t *block, const ScanScratch &s,
+void scan_launch(pm_ctx *ctx, const Jobs &J, const Jobs &L, int njobs, int64_t tiles, int64_t copies, int64_t places, bool emit, uint8_t *block, const ScanScratch &s,
                  int frame_waves, int packet_waves)
 {
     if (tiles) hipLaunchKernelGGL(bitscan_tile_kernel<Jobs>, dim3((unsigned)tiles), dim3(kLanes), 0, ctx->stream, J, block, s.sums);
-    hipLaunchKernelGGL(bitscan_combine_kernel<Jobs>, dim3(njobs), dim3(64), 0, ctx->stream, J, block, s.sums, s.carries, s.counts, s.steps_before);
-    if (emit && tiles) hipLaunchKernelGGL(bitscan_emit_kernel<Jobs>, dim3((unsigned)tiles), dim3(kLanes), 0, ctx->stream, J, block, s.carries, s.lists, s.cands);
-    if (copies) hipLaunchKernelGGL(bitscan_frames_kernel<Jobs>, dim3(frame_waves, njobs), dim3(64), 0, ctx->stream, J, block, s.lists, s.counts);
+    hipLaunchKernelGGL(bitscan_combine_kernel<Jobs>, dim3(njobs), dim3(64), 0, ctx->stream, J, block, s.sums, s.carries, s.counts, s.steps_before, s.carry_in);
+    if (emit && tiles) hipLaunchKernelGGL(bitscan_emit_kernel<Jobs>, dim3((unsigned)tiles), dim3(kLanes), 0, ctx->stream, L, block, s.carries, s.lists, s.cands);
+    if (copies) hipLaunchKernelGGL(bitscan_frames_kernel<Jobs>, dim3(frame_waves, njobs), dim3(64), 0, ctx->stream, L, block, s.lists, s.counts);
     if (places) {
         const int ptune = ctx->tune.bitscan_packet_waves;
-        hipLaunchKernelGGL(bitscan_headers_kernel<Jobs>, dim3(njobs), dim3(64), 0, ctx->stream, J, block, s.counts, s.cands, s.recs, s.work, s.pkcounts);
-        hipLaunchKernelGGL(bitscan_blocks_kernel<Jobs>, dim3(ptune > 0 ? std::min(ptune, 1024) : packet_waves, njobs), dim3(64), 0, ctx->stream, J, block, s.recs,
+        hipLaunchKernelGGL(bitscan_headers_kernel<Jobs>, dim3(njobs), dim3(64), 0, ctx->stream, L, block, s.counts, s.cands, s.recs, s.work, s.pkcounts);
+        hipLaunchKernelGGL(bitscan_blocks_kernel<Jobs>, dim3(ptune > 0 ? std::min(ptune, 1024) : packet_waves, njobs), dim3(64), 0, ctx->stream, L, block, s.recs,
                            s.work, s.pkcounts);
     }
 }
 
+// pm_scan_carry_set: one lane stores the seeded carry
+__global__ void carry_set_kernel(pm_scan_carry *d_carry, pm_scan_carry v) { *d_carry = v; }
+
 }  // namespace
+
+extern "C" int pm_scan_carry_set(pm_ctx *ctx, pm_scan_carry *d_carry, uint64_t lfsr_state, int32_t ones, int64_t counted)
+{
+    PM_CTX(ctx);
+    PM_ARG(d_carry && ((uintptr_t)d_carry & 7) == 0 && ones >= 0);
+    pm_scan_carry v;
+    memset(&v, 0, sizeof(v));
+    v.lfsr_state = lfsr_state;
+    v.ones = ones < 7 ? ones : 7;
+    v.tail = tail_of_ones(v.ones);
+    v.counted = counted;
+    v.state = counted < 0 ? PM_SCAN_CARRY_LOST : ones == 0 && counted == 0 ? PM_SCAN_CARRY_START : PM_SCAN_CARRY_OK;
+    hipLaunchKernelGGL(carry_set_kernel, dim3(1), dim3(1), 0, ctx->stream, d_carry, v);
+    PM_HIP(hipGetLastError());
+    return PM_OK;
+}
 
 extern "C" int pm_stream_scan(pm_ctx *ctx, const pm_scan_job *h_jobs, int njobs, void *d_block, size_t block_bytes, int64_t *h_offsets, size_t *h_used)
 {
@@ -872,6 +954,7 @@ extern "C" int pm_stream_scan(pm_ctx *ctx, const pm_scan_job *h_jobs, int njobs,
     J.frame_words = ftune > 0 ? std::min(ftune, 64) : 64;
     size_t at = 0;
     int64_t tiles = 0, copies = 0, places = 0;
+    bool any_carry = false;
     for (int j = 0; j < njobs; ++j) {
         const pm_scan_job &q = h_jobs[j];
         PM_ARG(q.n >= 0 && q.n <= (int64_t)1 << 29 && (q.n == 0 || (q.d_data && ((uintptr_t)q.d_data & 7) == 0)));
@@ -883,6 +966,13 @@ extern "C" int pm_stream_scan(pm_ctx *ctx, const pm_scan_job *h_jobs, int njobs,
         J.data[j] = q.d_data;
         J.poly[j] = q.lfsr_poly;
         J.reg0[j] = q.lfsr_state;
+        if (q.d_carry) {                                    // a piece of a stream: the register comes from the carry, whose pointer takes its place
+            PM_ARG(((uintptr_t)q.d_carry & 7) == 0);
+            for (int i = 0; i < j; ++i) PM_ARG(h_jobs[i].d_carry != q.d_carry);
+            J.reg0[j] = (uint64_t)(uintptr_t)q.d_carry;
+            J.carried[j] = 1;
+            any_carry = true;
+        }
         J.n[j] = (int32_t)q.n;
         J.kind[j] = (int8_t)q.codec_kind;
         J.invert[j] = q.lfsr_invert != 0;
@@ -906,6 +996,7 @@ extern "C" int pm_stream_scan(pm_ctx *ctx, const pm_scan_job *h_jobs, int njobs,
             places += q.n / 64 + 2;
         }
         if (q.addrs) at += (size_t)PM_SCAN_ADDR_BYTES(q.n);   // behind everything else of the part
+        if (q.d_carry) at += PM_SCAN_CARRY_BYTES;             // ... but the carry piece
         tiles += pm_cdiv(pm_cdiv(q.n, 8), J.tile_words);
         PM_ARG(tiles < (int64_t)1 << 30);
     }
@@ -913,10 +1004,13 @@ extern "C" int pm_stream_scan(pm_ctx *ctx, const pm_scan_job *h_jobs, int njobs,
     *h_used = at;
     if (at > block_bytes) return pm_set_error(PM_ERR_CAPACITY, "pm_stream_scan: the block holds %zu bytes, the batch needs %zu", block_bytes, at);
     ScanScratch s;
-    if (int rc = scan_scratch(ctx, kScanJobs, tiles, copies, places, 0, &s)) return rc;
+    if (int rc = scan_scratch(ctx, kScanJobs, tiles, copies, places, 0, &s, false, any_carry)) return rc;
+    ScanJobs L = J;                                         // behind the combine launch the carries are read from its copies
+    L.carry_in = s.carry_in;
+    L.late = 1;
     bool any = false;
     for (int j = 0; j < njobs; ++j) any = any || ((h_jobs[j].codec_kind == 0 || h_jobs[j].packets) && h_jobs[j].n > 0);
-    scan_launch(ctx, J, njobs, tiles, copies, places, any, static_cast<uint8_t *>(d_block), s, kFrameWaves, kPacketWaves);
+    scan_launch(ctx, J, L, njobs, tiles, copies, places, any, static_cast<uint8_t *>(d_block), s, kFrameWaves, kPacketWaves);
     PM_HIP(hipGetLastError());
     return PM_OK;
 }
@@ -980,7 +1074,7 @@ extern "C" int pm_rows_scan(pm_ctx *ctx, const pm_rowslice_rec *d_recs, const ui
     Entry *table = reinterpret_cast<Entry *>(s.extra);
     J.table = table;
     hipLaunchKernelGGL(rows_prepare_kernel, dim3(1), dim3(kLanes), 0, ctx->stream, J, d_recs, table, all);
-    scan_launch(ctx, J, nrows, all.tiles, all.events, all.places, any, static_cast<uint8_t *>(d_block), s, kRowFrameWaves, kRowPacketWaves);
+    scan_launch(ctx, J, J, nrows, all.tiles, all.events, all.places, any, static_cast<uint8_t *>(d_block), s, kRowFrameWaves, kRowPacketWaves);
     if (any_addrs && all.tiles)
         hipLaunchKernelGGL(rows_addrs_kernel, dim3((unsigned)all.tiles), dim3(kLanes), 0, ctx->stream, J, static_cast<uint8_t *>(d_block), s.steps_before);
     PM_HIP(hipGetLastError());

@@ -264,4 +264,52 @@ PM_EV_HD Listed emit_lane(const LaneIn &in, const TileCarry &c, int64_t B)
     return Listed{P0, F0, P1, F1, wanted, nothing};
 }
 
+// ---- a stream scanned in pieces (pm_scan_carry) -------------------------------------------------------------------------------------
+// A piece starts from what the piece before left: the bits in front of word 0 (`tail`, the last 64 descrambled bits, bit 63 the last) are
+// word 0's `prev`, and the combine starts `counted` bits behind a reset -- R = -counted, so that combine_step's span = P - R and
+// emit_lane's T are feed_many's T0 + (P - R) and span - dropped as they stand.  LOST starts kBailSpan bits behind one: the first reset bails.
+constexpr int kCarryStart = 0, kCarryOk = 1, kCarryLost = 2;        // PM_SCAN_CARRY_START / _OK / _LOST
+PM_EV_HD Combine combine_start_carried(int state, int64_t counted)
+{
+    Combine st = combine_start();
+    st.R = state == kCarryLost ? -(int64_t)kBailSpan : state == kCarryOk ? -counted : 0;
+    return st;
+}
+// The piece's last reset and the stuffed zeros behind it, over every tile, wherever a bail fell (TileSum's dropped, last_reset and
+// dropped_after_last do not depend on the bail).
+struct PieceEnd {
+    int64_t R, since;
+};
+PM_EV_HD PieceEnd piece_end_start(int64_t counted) { return PieceEnd{-counted, 0}; }
+PM_EV_HD void piece_end_step(PieceEnd &e, const TileSum &s, int64_t B)
+{
+    if (s.last_reset >= 0) {
+        e.R = B + s.last_reset + 1;
+        e.since = s.dropped_after_last;
+    } else {
+        e.since += s.dropped;
+    }
+}
+// `counted` behind a piece of n bytes that ends in `ones` ones (capped at 7).  The decoder clears its counters at the seventh one of a run
+// and at every one after it, in front of the zero that is the reset here: a piece that ends inside such a run hands on 0, as the
+// decoder's registers say, and the run's end in the next piece is a reset whatever was counted.
+PM_EV_HD int64_t piece_counted(const PieceEnd &e, int64_t n, int ones) { return ones >= 7 ? 0 : 8 * n - e.R - e.since; }
+// the state behind a piece: LOST if it started LOST or bailed
+PM_EV_HD int piece_state(int state_in, const Combine &st) { return state_in == kCarryLost || st.bail >= 0 ? kCarryLost : kCarryOk; }
+// the tail behind a piece: `last` holds the piece's last min(64, 8 n) bits, the stream's last bit on top of them (n >= 8: all 64)
+PM_EV_HD uint64_t tail_join(uint64_t tail, uint64_t last, int64_t n)
+{
+    if (n >= 8) return last;
+    if (n <= 0) return tail;
+    return (tail >> (8 * n)) | (last << (64 - 8 * n));
+}
+PM_EV_HD int tail_ones(uint64_t tail)
+{
+    const uint64_t z = ~tail;
+    const int k = z ? __builtin_clzll(z) : 64;
+    return k < 7 ? k : 7;
+}
+// the tail of a decoder with `ones` ones behind a zero (pm_codec.cpp: feed_many's prev)
+PM_EV_HD uint64_t tail_of_ones(int ones) { return ones >= 7 ? 0xFFull << 56 : ones > 0 ? ~0ull << (64 - ones) : 0; }
+
 }  // namespace pm_events

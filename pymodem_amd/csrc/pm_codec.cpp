@@ -155,16 +155,20 @@ struct pm_codec {
     int64_t walked = 0;                                  // bytes taken through the byte-by-byte machine (pm_codec_walked)
     int64_t fed = 0;
     int64_t addr_lookups = 0, addr_steps = 0;            // addresses resolved from a checkpoint, and the 16-bit steps added for them (pm_codec_addr_work)
+    int64_t next_piece = 0;                              // pm_codec_decode_carried: the piece of a stream scanned in pieces that comes next
     virtual ~pm_codec() {}
+    // the registers a pm_scan_carry is seeded from (pm_codec_scan_state)
+    virtual void scan_state(int32_t *ones, int64_t *counted) const { *ones = 0, *counted = 0; }
     // feed_many for a fresh decoder with the stream's pm_stream_scan record and list; false: the list does not fit the stream
     virtual bool feed_scanned(const uint8_t *d, const int64_t *a, int64_t n, const uint8_t *scan) = 0;
     // the same with the frame table and the frame area of a block made with pm_scan_job.frames (AX.25 only)
-    virtual bool feed_framed(const uint8_t *, const int64_t *, int64_t, const uint8_t *) { return false; }
+    // (piece: the part was made with a carry -- pm_codec_decode_carried -- and a "not made" first entry of the frame table is taken)
+    virtual bool feed_framed(const uint8_t *, const int64_t *, int64_t, const uint8_t *, bool /*piece*/) { return false; }
     // the same with the packet table and the packet area of a block made with pm_scan_job.packets (IL2P only)
     virtual bool feed_packets(const uint8_t *, const int64_t *, int64_t, const uint8_t *) { return false; }
     // the three with the addresses behind checkpoints (pm_bitscan_addrs.h): the same text, instantiated for the look-up instead of the pointer
     virtual bool feed_scanned(const uint8_t *d, pm_addrs::Ref a, int64_t n, const uint8_t *scan) = 0;
-    virtual bool feed_framed(const uint8_t *, pm_addrs::Ref, int64_t, const uint8_t *) { return false; }
+    virtual bool feed_framed(const uint8_t *, pm_addrs::Ref, int64_t, const uint8_t *, bool /*piece*/) { return false; }
     virtual bool feed_packets(const uint8_t *, pm_addrs::Ref, int64_t, const uint8_t *) { return false; }
     virtual void feed(uint8_t byte, int64_t addr, Sink &sink) = 0;
     virtual void feed_many(const uint8_t *d, const int64_t *a, int64_t n)
@@ -296,6 +300,12 @@ struct Ax25 : pm_codec {
         return x;
     }
 
+    void scan_state(int32_t *o, int64_t *counted) const override
+    {
+        *o = ones < 7 ? ones : 7;
+        *counted = (int64_t)nbytes * 8 + nbits;
+    }
+
     void reposition(const uint8_t *d, int64_t sb)
     {
         // byte sb holds a flag's closing zero: whatever the registers are in front of it, they are the decoder's own behind it -- and with
@@ -408,10 +418,10 @@ struct Ax25 : pm_codec {
 
     // feed_scanned with the frames themselves from the device: every listed flag's frame is queued as the frame area holds it, and only
     // what lies behind the stream's last flag (or behind the last flag in front of a bail) goes through the registers
-    bool feed_framed(const uint8_t *d, const int64_t *a, int64_t n, const uint8_t *scan) override { return framed(d, a, n, scan); }
-    bool feed_framed(const uint8_t *d, pm_addrs::Ref a, int64_t n, const uint8_t *scan) override { return framed(d, a, n, scan); }
+    bool feed_framed(const uint8_t *d, const int64_t *a, int64_t n, const uint8_t *scan, bool piece) override { return framed(d, a, n, scan, piece); }
+    bool feed_framed(const uint8_t *d, pm_addrs::Ref a, int64_t n, const uint8_t *scan, bool piece) override { return framed(d, a, n, scan, piece); }
     template <class A>
-    bool framed(const uint8_t *d, A a, int64_t n, const uint8_t *scan)
+    bool framed(const uint8_t *d, A a, int64_t n, const uint8_t *scan, bool piece)
     {
         if (!skim_on || n < 24) {
             run(d, a, 0, n);
@@ -423,7 +433,7 @@ struct Ax25 : pm_codec {
         memcpy(&events, scan + 24, 4);
         if (events < 0 || events > n / 19 + 2 || last_flag < -1 || last_flag > 8 * n) return false;
         const uint8_t *table = scan + PM_SCAN_HEAD + PM_SCAN_LIST_BYTES(0, n) + (n + 7) / 8 * 8, *area = table + PM_SCAN_FRAME_TABLE_BYTES(n);
-        int64_t cursor = 0;
+        int64_t cursor = 0, taken = 0;                       // taken: bytes that the registers have been through
         for (int32_t e = 0; e < events; ++e) {
             uint32_t pf[2], crc;
             int32_t len;
@@ -432,6 +442,11 @@ struct Ax25 : pm_codec {
             memcpy(&crc, table + 8 * (size_t)e + 4, 4);
             const int64_t P = pf[0], F = pf[1] == 0xFFFFFFFFu ? -1 : (int64_t)pf[1];
             if ((P >> 3) >= n || F > P || (P >> 3) + 1 < cursor) return false;
+            if (piece && len == -1 && e == 0 && F < 0) {              // a later piece's first listed flag, "not made": what it closes began in an earlier piece
+                run(d, a, 0, (P >> 3) + 1);
+                cursor = taken = (P >> 3) + 1;
+                continue;
+            }
             cursor = (P >> 3) + 1;
             const int64_t from = F < 0 ? 0 : F, at = from >> 3;
             if (len < 0 || len > (P - from) / 8 || at + len > n || crc > 0xFFFFu) return false;
@@ -439,6 +454,10 @@ struct Ax25 : pm_codec {
         }
         // feed_scanned's last step.  The byte that holds the last flag's closing zero is taken again: with no byte counted the flag closes nothing
         const int64_t sb = last_flag >= 0 ? (last_flag - 1) >> 3 : 0;
+        if (sb < taken) {                                    // (the not-made flag is the last one: the registers stand behind its byte)
+            run(d, a, taken, n);
+            return true;
+        }
         if (sb > 0) reposition(d, sb);
         run(d, a, sb, n);
         return true;
@@ -1198,7 +1217,7 @@ int pm_codec_decode_framed(pm_codec *c, const uint8_t *h_plain, const int64_t *h
     if (!c->fresh) return pm_set_error(PM_ERR_ARG, "pm_codec_decode_framed: the codec has been fed before (the lists are made for a just-created decoder)");
     c->fresh = false;
     c->fed += n;
-    if (!c->feed_framed(h_plain, h_addr, n, static_cast<const uint8_t *>(h_scan)))
+    if (!c->feed_framed(h_plain, h_addr, n, static_cast<const uint8_t *>(h_scan), false))
         return pm_set_error(PM_ERR_ARG, "pm_codec_decode_framed: the event list or the frame table does not belong to a stream of %lld bytes", (long long)n);
     *h_pending = (int64_t)c->sink.q.size();
     return PM_OK;
@@ -1237,13 +1256,84 @@ int pm_codec_decode_addrs(pm_codec *c, const uint8_t *h_plain, const uint16_t *h
                             (long long)addr_first);
     pm_addrs::Lookup look{scan + at, h_steps, 0, 0};
     const pm_addrs::Ref a{&look};
-    const bool ok = frames ? c->feed_framed(h_plain, a, n, scan) : packets ? c->feed_packets(h_plain, a, n, scan) : c->feed_scanned(h_plain, a, n, scan);
+    const bool ok = frames ? c->feed_framed(h_plain, a, n, scan, false) : packets ? c->feed_packets(h_plain, a, n, scan) : c->feed_scanned(h_plain, a, n, scan);
     c->addr_lookups += look.lookups;
     c->addr_steps += look.nsteps;
     if (!ok) return pm_set_error(PM_ERR_ARG, "pm_codec_decode_addrs: the lists do not belong to a stream of %lld bytes", (long long)n);
     c->fresh = false;
     c->fed += n;
     *h_pending = (int64_t)c->sink.q.size();
+    return PM_OK;
+}
+
+// The scanned routes for a piece of a stream (pm_scan_job.d_carry): the same three routes from whatever state the codec is in, once the
+// carry piece at the part's end has been held against it.
+int pm_codec_decode_carried(pm_codec *c, const uint8_t *h_plain, const int64_t *h_addr, const uint16_t *h_steps, int64_t addr_first, int64_t n,
+                            const void *h_scan, int32_t frames, int32_t packets, int32_t addrs, int64_t *h_pending)
+{
+    if (!c || n < 0 || (n > 0 && (!h_plain || (!h_addr && !h_steps))) || !h_scan || !h_pending || (frames && packets) || (addrs && (h_addr || !h_steps) && n > 0))
+        return pm_set_error(PM_ERR_ARG, "pm_codec_decode_carried: bad argument");
+    if ((frames && c->kind != 0) || (packets && c->kind != 1))
+        return pm_set_error(PM_ERR_ARG, "pm_codec_decode_carried: frames are made for AX.25 codecs only, packets for IL2P codecs only");
+    const uint8_t *scan = static_cast<const uint8_t *>(h_scan);
+    int64_t at = PM_SCAN_HEAD + PM_SCAN_LIST_BYTES(c->kind, n) + (n + 7) / 8 * 8;
+    if (frames) at += PM_SCAN_FRAME_TABLE_BYTES(n) + PM_SCAN_FRAME_AREA_BYTES(n);
+    if (packets) at += PM_SCAN_PACKET_TABLE_BYTES(n) + PM_SCAN_PACKET_AREA_BYTES(n);
+    const uint8_t *ckpt = scan + at;
+    if (addrs) at += PM_SCAN_ADDR_BYTES(n);
+    int32_t state, ones;
+    int64_t counted, piece;
+    memcpy(&state, scan + at, 4);
+    memcpy(&ones, scan + at + 4, 4);
+    memcpy(&counted, scan + at + 8, 8);
+    memcpy(&piece, scan + at + 16, 8);
+    if (state < PM_SCAN_CARRY_START || state > PM_SCAN_CARRY_LOST)
+        return pm_set_error(PM_ERR_ARG, "pm_codec_decode_carried: the part does not end with a carry piece (state %d)", (int)state);
+    if (c->kind == 0 && (state == PM_SCAN_CARRY_START) != c->fresh)
+        return pm_set_error(PM_ERR_ARG, "pm_codec_decode_carried: the carry piece says %s, the codec has %s", state == PM_SCAN_CARRY_START ? "START" : "a stream under way",
+                            c->fresh ? "never been fed" : "been fed");
+    if (piece != 0 && piece != c->next_piece)
+        return pm_set_error(PM_ERR_ARG, "pm_codec_decode_carried: piece %lld, the codec's next one is %lld", (long long)piece, (long long)c->next_piece);
+    if (c->kind == 0) {
+        int32_t my_ones;
+        int64_t my_counted;
+        c->scan_state(&my_ones, &my_counted);
+        if (state == PM_SCAN_CARRY_OK && counted < 8000 && my_counted < 8000 && (ones != my_ones || counted != my_counted))
+            return pm_set_error(PM_ERR_ARG, "pm_codec_decode_carried: the carry piece has ones %d, counted %lld, the codec %d, %lld", (int)ones, (long long)counted,
+                                (int)my_ones, (long long)my_counted);
+    }
+    bool ok;
+    if (addrs) {
+        if (!pm_addrs::table_fits(ckpt, n, addr_first))
+            return pm_set_error(PM_ERR_ARG, "pm_codec_decode_carried: the checkpoint table does not belong to a stream of %lld bytes that begins at address %lld",
+                                (long long)n, (long long)addr_first);
+        pm_addrs::Lookup look{ckpt, h_steps, 0, 0};
+        const pm_addrs::Ref a{&look};
+        ok = frames ? c->feed_framed(h_plain, a, n, scan, true) : packets ? c->feed_packets(h_plain, a, n, scan) : c->feed_scanned(h_plain, a, n, scan);
+        c->addr_lookups += look.lookups;
+        c->addr_steps += look.nsteps;
+    } else {
+        std::vector<int64_t> wide;
+        if (!h_addr && n > 0) {
+            wide.resize((size_t)n);
+            int64_t a = addr_first;
+            for (int64_t i = 0; i < n; ++i) wide[(size_t)i] = (a += h_steps[i]);
+            h_addr = wide.data();
+        }
+        ok = frames ? c->feed_framed(h_plain, h_addr, n, scan, true) : packets ? c->feed_packets(h_plain, h_addr, n, scan) : c->feed_scanned(h_plain, h_addr, n, scan);
+    }
+    if (!ok) return pm_set_error(PM_ERR_ARG, "pm_codec_decode_carried: the lists do not belong to a stream of %lld bytes", (long long)n);
+    c->fresh = false;
+    c->fed += n;
+    c->next_piece = piece + 1;
+    *h_pending = (int64_t)c->sink.q.size();
+    return PM_OK;
+}
+
+int pm_codec_scan_state(pm_codec *c, int32_t *h_ones, int64_t *h_counted)
+{
+    if (!c || !h_ones || !h_counted) return pm_set_error(PM_ERR_ARG, "pm_codec_scan_state: bad argument");
+    c->scan_state(h_ones, h_counted);
     return PM_OK;
 }
 
@@ -1314,6 +1404,15 @@ int pm_host_decode_batch(pm_host_job *jobs, int njobs, int threads)
         thread_local std::vector<int64_t> wide;
         if (!q.h_plain && !q.h_scan && (int64_t)plain.size() < q.n) plain.resize((size_t)q.n);
         const int64_t *addr = q.h_addr;
+        if (q.h_scan && q.scan_carry) {                      // a piece of a stream scanned in pieces: the codec may be in any state
+            const uint8_t *scan = static_cast<const uint8_t *>(q.h_scan);
+            const uint8_t *bytes = scan + PM_SCAN_HEAD + PM_SCAN_LIST_BYTES(q.codec->kind, q.n);
+            if (q.h_plain && q.n > 0) memcpy(q.h_plain, bytes, (size_t)q.n);
+            memcpy(&q.lfsr_state, scan, 8);
+            q.status = pm_codec_decode_carried(q.codec, bytes, addr, q.h_addr_delta, q.addr_first, q.n, scan, q.scan_frames, q.scan_packets, !addr && q.scan_addrs,
+                                               &q.pending);
+            return;
+        }
         if (!addr && q.h_scan && q.scan_addrs) {             // the block has checkpoints: an address is resolved where a decoder asks for one
             const uint8_t *scan = static_cast<const uint8_t *>(q.h_scan);
             const uint8_t *bytes = scan + PM_SCAN_HEAD + PM_SCAN_LIST_BYTES(q.codec->kind, q.n);

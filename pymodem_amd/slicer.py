@@ -208,6 +208,7 @@ def _slice_group(ctx, slicers, bitmaps, group, out, tight, reserve=1.0, out_tag=
                 else:
                     out[k] = AddressedArray.from_steps(data, steps, first)
         fetch_compact.room = dense.n
+        fetch_compact.device = (jobs, block, counts, a_off, d_off)
         return fetch_compact
 
     def fetch(copy_ctx=None):
@@ -215,6 +216,9 @@ def _slice_group(ctx, slicers, bitmaps, group, out, tight, reserve=1.0, out_tag=
         for j, k in enumerate(group):
             # views into this call's own download (a fresh array every call): no second copy
             out[k] = AddressedArray(host[d_off[j]:d_off[j] + counts[j]], host[a_off[j]:a_off[j] + counts[j] * 8].view(np.int64))
+    # what the batch left on the device, for a caller that goes on there (scanned.ScannedChain): the jobs as pm_slice_batch filled them,
+    # the block their d_data / d_addr point into, the counts and the streams' offsets of addresses and bytes in the block
+    fetch.device = (jobs, block, counts, a_off, d_off)
     return fetch
 
 
