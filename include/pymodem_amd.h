@@ -619,6 +619,43 @@ typedef struct pm_rows_scan_chain {
 int pm_rows_scan(pm_ctx *ctx, const pm_rowslice_rec *d_recs, const uint8_t *d_data, const uint16_t *d_steps, int64_t cap, int64_t row0, int nrows,
                  const pm_rows_scan_chain *h_chains, int nchains, const int64_t *h_counts, void *d_block, size_t block_bytes, int64_t *h_offsets,
                  size_t *h_used);
+/* Rows scanned in PIECES: pm_rows_scan with pm_stream_scan's carry (pm_scan_job.d_carry) per row, so that the rows of a run can be taken
+ * time chunk by time chunk with nothing waiting for the host.  d_carries: one pm_rows_carry per row of the RUN, in device memory, owned by
+ * the caller, 8-byte aligned, indexed by row (row0 + r).  pm_rows_carry_start sets rows [row0, row0 + nrows) to state START with their
+ * chain's lfsr_state and taken = 0, in one launch on the ctx stream.  pm_scan_carry_set on &d_carries[row].scan re-seeds a row (behind a
+ * bail: state LOST) and leaves taken and last_addr alone.
+ * The piece of row row0 + r is decided on the device, in the call's first launch, from the record's count and the carry:
+ *       avail = min(d_upto ? d_upto[r] : count, min(count, cap)),  from = taken,
+ *       n = avail - from, rounded down to a multiple of 8 unless `final`, never below 0.
+ * All but the final cut are multiples of 8: a row begins on an 8-byte boundary (cap is a multiple of 8), so every piece's bytes and its
+ * steps at d_steps + row * cap + from keep their 8-byte alignment; up to seven bytes held back go with the next piece.  A row whose
+ * `taken` is no multiple of 8 has had its final piece and gives empty pieces from then on.  An empty piece is a piece: record, carry piece,
+ * scan.pieces + 1.  d_upto (device, int64 per r, 8-byte aligned) may be NULL: the records' counts.  h_counts[r] must be that same n -- the
+ * host knows what it passed as upto, the counts where they matter, and what it has taken; a row whose part would pass what h_counts sized is
+ * left out: no launch stores anything for it, in block, scratch or carry.
+ * For row r, at d_block + h_offsets[r]: what pm_rows_scan writes for a row of these n bytes -- the piece's n steps padded to 8, the scan part,
+ * with addrs the checkpoints -- and behind it PM_ROWS_PIECE_TAIL_BYTES: the job form's carry piece (the carry-in echoed, PM_SCAN_CARRY_BYTES)
+ * and int64 addr_before, the stream address of the byte in front of the piece: d_recs[row].first_addr while taken == 0 (where the row's
+ * first step is 0), last_addr after that.  The address of the piece's byte i is addr_before + steps[0] + ... + steps[i] -- the piece's first
+ * step counts -- and a checkpoint is A[w] = addr_before + steps[0 .. 64 w].
+ * Every launch takes from the carry what pm_stream_scan's launches take from pm_scan_job.d_carry, the tile and combine launches from the
+ * carry itself, those behind them from a copy in context scratch: the register in front of word 0, the tail, START or not, the counted
+ * bits, the "not made" entry for a first listed flag that closes a frame from an earlier piece; an IL2P attempt that runs past the piece is
+ * INCOMPLETE; a bail writes LOST as the carry-out.  Lane 0 of the combine wave is the carry's only writer: scan as the job form leaves it,
+ * taken += n, last_addr = addr_before + the piece's steps.
+ * Arguments as for pm_rows_scan; d_carries non-NULL and 8-byte aligned, d_upto 8-byte aligned when given.  nrows <= 4096, nchains <= 64,
+ * PM_ERR_CAPACITY with *h_used set, nothing uploaded, allocated beyond context scratch or waited for.  Two calls for the same rows must
+ * follow each other on one context's stream. */
+#define PM_ROWS_PIECE_TAIL_BYTES 40
+typedef struct pm_rows_carry {
+    pm_scan_carry scan;              /* exactly the job form's carry */
+    int64_t taken;                   /* bytes of the row that earlier pieces took: where the next piece begins */
+    int64_t last_addr;               /* stream address of byte taken - 1 (meaningless while taken == 0) */
+} pm_rows_carry;
+int pm_rows_carry_start(pm_ctx *ctx, pm_rows_carry *d_carries, int64_t row0, int nrows, const pm_rows_scan_chain *h_chains, int nchains);
+int pm_rows_scan_pieces(pm_ctx *ctx, const pm_rowslice_rec *d_recs, const uint8_t *d_data, const uint16_t *d_steps, int64_t cap, int64_t row0, int nrows,
+                        const pm_rows_scan_chain *h_chains, int nchains, pm_rows_carry *d_carries, const int64_t *d_upto, int32_t final,
+                        const int64_t *h_counts, void *d_block, size_t block_bytes, int64_t *h_offsets, size_t *h_used);
 pm_ctx *pm_lbatch_front_ctx(pm_lbatch *batch);       /* the engine's own contexts, for pm_prof_*: band-pass, AGC, Hilbert of chunk t + 1 ... */
 pm_ctx *pm_lbatch_tail_ctx(pm_lbatch *batch);        /* ... and the matched filters of chunk t - 1, beside the loops of chunk t on the caller's */
 pm_ctx *pm_lbatch_loop_ctx(pm_lbatch *batch);        /* ... or on the engine's loop context, when the loops have compute units of their own (else NULL) */
@@ -700,7 +737,9 @@ int pm_codec_decode_addrs(pm_codec *c, const uint8_t *h_plain, const uint16_t *h
                           int32_t packets, int64_t *h_pending);
 /* The scanned routes for a part made with pm_scan_job.d_carry, for a codec in ANY state: the next piece of a stream that is scanned in
  * pieces.  frames, packets, addrs: how the part was made; the addresses come as h_addr (n of them), or, with h_addr NULL, as h_steps and
- * addr_first (with addrs they are resolved from the checkpoints as in pm_codec_decode_addrs, without addrs they are expanded).  The part
+ * addr_first (with addrs they are resolved from the checkpoints as in pm_codec_decode_addrs, without addrs they are expanded).  Here
+ * h_steps[0] counts: byte 0's address is addr_first + h_steps[0], and that is what A[0] must be -- 0 for a stream's first piece, not 0 for
+ * a later piece of a row (pm_rows_scan_pieces), whose addr_first is its addr_before.  The part
  * ends with the carry piece, which must agree with the codec: for an AX.25 codec state START goes with a codec that has never been fed and
  * state OK with one whose `ones` and `counted` (pm_codec_scan_state) are the carry piece's -- compared only while both counts are below
  * 8000 bits; state LOST goes with any.  (An IL2P codec's attempts depend on nothing in front of the piece: only the piece number counts.)

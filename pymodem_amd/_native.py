@@ -127,6 +127,20 @@ class RowsScanChain(ctypes.Structure):
                 ("addrs", ctypes.c_int32)]
 
 
+class RowsCarry(ctypes.Structure):
+    """pm_rows_carry"""
+    _fields_ = [("scan", ScanCarry), ("taken", ctypes.c_int64), ("last_addr", ctypes.c_int64)]
+
+
+ROWS_PIECE_TAIL_BYTES = 40                                      # PM_ROWS_PIECE_TAIL_BYTES
+
+
+def rows_carry_dtype():
+    """NumPy view of a pm_rows_carry."""
+    import numpy as np
+    return np.dtype([("scan", scan_carry_dtype()), ("taken", "<i8"), ("last_addr", "<i8")])
+
+
 SCAN_HEAD = 32        # PM_SCAN_HEAD
 SCAN_ADDR_STRIDE = 64  # PM_SCAN_ADDR_STRIDE
 
@@ -177,6 +191,11 @@ def scan_part_bytes(kind, frames, packets, n, addrs=0):
 def rows_scan_steps_bytes(n):
     """The address steps in front of a row's scan part in a pm_rows_scan block (pm_rows::steps_bytes)."""
     return (2 * n + 7) // 8 * 8
+
+
+def rows_piece_part_bytes(kind, frames, packets, n, addrs=0):
+    """A row's part in a pm_rows_scan_pieces block (pm_rows::piece_part_bytes): the piece's steps, its scan part, the carry piece and addr_before."""
+    return rows_scan_steps_bytes(n) + scan_part_bytes(kind, frames, packets, n, addrs) + ROWS_PIECE_TAIL_BYTES
 
 
 def scan_packet_dtype():
@@ -350,6 +369,9 @@ _SIGS = {
     "pm_rows_gather": ([_vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, ctypes.c_size_t], _int),
     "pm_rows_scan": ([_vp, _vp, _vp, _vp, _i64, _i64, _int, ctypes.POINTER(RowsScanChain), _int, ctypes.POINTER(_i64), _vp, ctypes.c_size_t,
                      ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_size_t)], _int),
+    "pm_rows_carry_start": ([_vp, _vp, _i64, _int, ctypes.POINTER(RowsScanChain), _int], _int),
+    "pm_rows_scan_pieces": ([_vp, _vp, _vp, _vp, _i64, _i64, _int, ctypes.POINTER(RowsScanChain), _int, _vp, _vp, ctypes.c_int32, ctypes.POINTER(_i64), _vp,
+                            ctypes.c_size_t, ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_size_t)], _int),
     "pm_lbatch_run": ([_vp, ctypes.POINTER(_vp), _int, _i64, _vp, _vp, _i64, ctypes.POINTER(_i64)], _int),
     "pm_lbatch_front_ctx": ([_vp], _vp),
     "pm_lbatch_tail_ctx": ([_vp], _vp),

@@ -150,6 +150,72 @@ def _host_stages_scanned(chains, fetched, frames=False, packets=False, addrs=Fal
     return [rows_to_packets(v, ch[4].identifier) for ch, v in zip(chains, _host_rows_scanned(chains, fetched, None, frames, packets, addrs))]
 
 
+def _host_rows_pieces(chains, fetched, chain_ids=None, frames=False, packets=False, addrs=False, raw=None):
+    """_host_rows_scanned for the next PIECE of every chain's row (loop_batch.RowPieces.fetch): fetched[j] = (the piece's address steps, the
+    address in front of the piece, n, the piece's scan part with its carry piece).  The codecs may be in any state (pm_host_job.scan_carry ->
+    pm_codec_decode_carried); addr_first is the piece's addr_before, and the piece's first step counts.  A part that the host route refuses with
+    the codec untouched goes the ordinary way -- raw(j) -> the piece's slicer bytes as an AddressedArray, through the host's LFSR and the codec's
+    own search.  -> (row blocks per chain, [(j, LFSR register, ones, counted)] for the rows whose carry has to be seeded again before their next
+    piece -- a bail, a LOST carry, or the ordinary way -- and how many went the ordinary way)."""
+    import ctypes
+    from ._native import SCAN_CARRY_BYTES, SCAN_CARRY_LOST, SCAN_HEAD, HostJob, check, lib, packet_dtype, quick, scan_carry_piece_dtype, scan_record_dtype
+    n = len(chains)
+    jobs = (HostJob * n)()
+
+    def fed(j):
+        w, jumped = ctypes.c_int64(), ctypes.c_int64()
+        check(lib().pm_codec_walked(jobs[j].codec, ctypes.byref(w), ctypes.byref(jumped)))     # (lib(): its argument types are declared)
+        return w.value + jumped.value
+    for j, (ch, (steps, before, count, scan)) in enumerate(zip(chains, fetched)):
+        jobs[j].codec = ch[4]._handle()
+        if chain_ids is not None:
+            quick().pm_codec_set_source(jobs[j].codec, int(chain_ids[j]))
+        jobs[j].h_data, jobs[j].h_addr, jobs[j].n = None, None, int(count)
+        jobs[j].h_addr_delta, jobs[j].addr_first = (steps.ctypes.data if count else None), int(before)
+        jobs[j].h_scan = scan.ctypes.data
+        jobs[j].scan_frames, jobs[j].scan_packets = int(bool(frames) and ch[4]._kind == 0), int(bool(packets) and ch[4]._kind == 1)
+        jobs[j].scan_addrs, jobs[j].scan_carry = int(bool(addrs)), 1
+        jobs[j].lfsr_poly, jobs[j].lfsr_state, jobs[j].lfsr_invert = ch[3].polynomial, ch[3].shift_register, int(bool(ch[3].invert))
+    before_fed = [fed(j) for j in range(n)]
+    threads = _host_threads()
+    rc = lib().pm_host_decode_batch(jobs, n, threads)
+    pending, again, ordinary = [], [], 0
+    for j, (ch, (steps, before, count, scan)) in enumerate(zip(chains, fetched)):
+        lost = False
+        if jobs[j].status == 0:
+            ch[3].shift_register = jobs[j].lfsr_state       # the registers are taken back from the records
+            pending.append(int(jobs[j].pending))
+            rec = scan[:SCAN_HEAD].view(scan_record_dtype())[0]
+            piece = scan[len(scan) - SCAN_CARRY_BYTES:].view(scan_carry_piece_dtype())[0]
+            lost = int(piece["state"]) == SCAN_CARRY_LOST or (ch[4]._kind == 0 and int(rec["bail_bit"]) >= 0)
+        elif raw is not None and fed(j) == before_fed[j]:     # refused with the codec untouched: nothing is lost, the piece goes the ordinary way
+            pending.append(int(ch[4].decode_pending(ch[3].stream_unscramble_8bit(raw(j)))))
+            ordinary += 1
+            lost = True
+        else:
+            check(rc if rc else jobs[j].status)
+        if lost:
+            ones, counted = ctypes.c_int32(), ctypes.c_int64()
+            check(lib().pm_codec_scan_state(jobs[j].codec, ctypes.byref(ones), ctypes.byref(counted)))
+            again.append((j, int(ch[3].shift_register), ones.value, counted.value))
+    counts = (ctypes.c_int64 * n)(*pending)
+    handles = (ctypes.c_void_p * n)(*[jobs[j].codec for j in range(n)])
+    block = np.empty(sum(counts), dtype=packet_dtype())
+    check(lib().pm_codec_fetch_batch(handles, counts, n, block.ctypes.data_as(ctypes.c_void_p), threads))
+    views, at = [], 0
+    for c in counts:
+        views.append(block[at:at + c])
+        at += c
+    return views, again, ordinary
+
+
+def _host_stages_pieces(chains, fetched, frames=False, packets=False, addrs=False, raw=None):
+    """_host_rows_pieces with PacketMeta lists in the row blocks' place."""
+    from .packet_meta import rows_to_packets
+    views, again, ordinary = _host_rows_pieces(chains, fetched, None, frames, packets, addrs, raw)
+    return [rows_to_packets(v, ch[4].identifier) for ch, v in zip(chains, views)], again, ordinary
+
+
 _POOL = None
 _USE_SWEEP = True          # pm_afsk_sweep_signs for gain sweeps (tests switch it off to compare against the exact group path)
 _GROUP_RUN_QUICK = [__import__("os").environ.get("PYMODEM_AMD_GROUP_RUN_QUICK", "0") != "0"]     # measured: submit 0.16 ms instead of 0.4, the step unchanged

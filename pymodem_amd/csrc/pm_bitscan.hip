@@ -27,6 +27,9 @@
 // of it come from the carry, the combine launch starts from the carry's counted bits instead of from a just-created decoder's state, and
 // its lane 0 echoes the carry-in into the carry piece at the part's end and into scratch, then writes the carry-out.  The launches behind
 // it read the scratch copy, never d_carry, so the pieces of a stream follow each other on the stream without the host in between.
+// pm_rows_scan_pieces is the row form with such a carry per row (pm_rows_carry): a third source, RowPieceJobs, whose table entries say where in
+// its row a piece begins and which address lies in front of it; the prepare launch cuts the pieces from the carries' `taken`, and the combine
+// launch's lane 0 moves `taken` and `last_addr` on beside the carry-out.
 #include "pm_common.h"
 #include "pm_bitscan_addrs.h"
 #include "pm_bitscan_events.h"
@@ -101,6 +104,9 @@ struct ScanJobs {
     }
     __device__ void copy_steps(uint8_t *, const Job &, int, int64_t) const {}      // (the job form's block has no steps)
     __device__ void load_steps(int, int64_t, uint64_t *, uint64_t *) const {}
+    static constexpr bool kPieces = false;  // (rows in pieces: RowPieceJobs)
+    __device__ static uint32_t lane_sum(uint64_t lo, uint64_t hi, int64_t w, int64_t n) { return pm_addrs::lane_sum(lo, hi, w, n); }
+    __device__ void piece_end(int, int64_t *, int64_t, int64_t) const {}
 };
 static_assert(sizeof(ScanJobs) + 64 <= 4096, "the table goes to the kernels by value, with up to eight pointers beside it");
 
@@ -145,6 +151,67 @@ struct RowJobs {
         const uint64_t *src = reinterpret_cast<const uint64_t *>(steps + (row0 + j) * cap);      // cap is a multiple of 8: rows are aligned
         uint64_t *dst = reinterpret_cast<uint64_t *>(block + jb.off) - sw;
         for (int64_t i = 2 * w; i < 2 * w + 2 && i < sw; ++i) dst[i] = src[i];
+    }
+    static constexpr bool kPieces = false;
+    __device__ static uint32_t lane_sum(uint64_t lo, uint64_t hi, int64_t w, int64_t n) { return pm_addrs::lane_sum(lo, hi, w, n); }
+    __device__ static uint32_t lane_first(uint64_t lo, int64_t w) { return pm_addrs::lane_first(lo, w); }
+    __device__ int64_t addr_before(int j) const { return recs[row0 + j].first_addr; }      // (the row's first step is not added: the first byte's own)
+    __device__ void piece_end(int, int64_t *, int64_t, int64_t) const {}
+};
+
+// pm_rows_scan_pieces' source: RowJobs' fields, with a table whose entries say where in its row a piece begins (pm_rows::PieceEntry) and the
+// rows' carries.  A job is the piece of row row0 + j that begins `from` bytes into the row, with &carries[row0 + j].scan for its d_carry.
+struct RowPieceJobs : RowJobs {
+    const pm_rows::PieceEntry *ptable;      // nrows + 1 entries, the last one the totals
+    pm_rows_carry *carries;                 // indexed by row
+    const pm_scan_carry *carry_in;          // the carries as the pieces found them, indexed by j (ScanJobs::carry_in) ...
+    int32_t late;                           // ... for the launches behind the combine
+
+    __device__ int tiles() const { return ptable[nrows].tile0; }
+    __device__ int job_of_tile(int tile) const
+    {
+        const pm_rows::PieceEntry *t = ptable;
+        return pm_rows::row_of_tile([t](int i) { return t[i].tile0; }, nrows, tile);
+    }
+    __device__ Job job(int j) const
+    {
+        const pm_rows::PieceEntry e = ptable[j];
+        const int c = (int)((row0 + j) % nchains);
+        Job jb{data + (row0 + j) * cap + e.from, poly[c], reg0[c], e.off + pm_rows::steps_bytes(e.n), e.ev0, e.pk0, e.n, e.tile0, ptable[j + 1].tile0,
+               kind[c], invert[c], tol[c], pkopt[c], e.off >= 0, nullptr, addrs[c] != 0, 0, nullptr, false};
+        jb.carry = &carries[row0 + j].scan;
+        const pm_scan_carry *cy = late ? carry_in + j : jb.carry;
+        jb.reg0 = cy->lfsr_state;
+        jb.tail = cy->tail;
+        jb.started = cy->state != PM_SCAN_CARRY_START;
+        return jb;
+    }
+    // (a piece with bytes begins at a multiple of 8 and ends inside the row: 8 w < n gives from + 8 w + 8 <= cap)
+    __device__ void load_steps(int j, int64_t w, uint64_t *lo, uint64_t *hi) const
+    {
+        const uint64_t *src = reinterpret_cast<const uint64_t *>(steps + (row0 + j) * cap + ptable[j].from);
+        *lo = src[2 * w];
+        *hi = src[2 * w + 1];
+    }
+    __device__ void copy_steps(uint8_t *block, const Job &jb, int j, int64_t w) const
+    {
+        const int64_t sw = pm_rows::steps_bytes(jb.n) >> 3;
+        const uint64_t *src = reinterpret_cast<const uint64_t *>(steps + (row0 + j) * cap + ptable[j].from);
+        uint64_t *dst = reinterpret_cast<uint64_t *>(block + jb.off) - sw;
+        for (int64_t i = 2 * w; i < 2 * w + 2 && i < sw; ++i) dst[i] = src[i];
+    }
+    static constexpr bool kPieces = true;   // the tile launch sums every row's steps, with step 0: last_addr needs them
+    __device__ static uint32_t lane_sum(uint64_t lo, uint64_t hi, int64_t w, int64_t n) { return pm_addrs::piece_lane_sum(lo, hi, w, n); }
+    __device__ static uint32_t lane_first(uint64_t lo, int64_t) { return pm_addrs::piece_lane_first(lo); }
+    __device__ int64_t addr_before(int j) const { return ptable[j].addr_before; }
+    // the combine launch's lane 0, behind the carry-out: addr_before behind the carry piece, and where the row's next piece begins
+    __device__ void piece_end(int j, int64_t *piece, int64_t n, int64_t steps_sum) const
+    {
+        const pm_rows::PieceEntry e = ptable[j];
+        piece[4] = e.addr_before;
+        pm_rows_carry *c = carries + row0 + j;
+        c->taken = e.from + n;
+        c->last_addr = e.addr_before + steps_sum;
     }
 };
 struct PkRec {                              // the headers launch's copy of a record for the blocks launch, with the 13 descrambled header bytes
@@ -296,10 +363,10 @@ __global__ __launch_bounds__(kLanes) void bitscan_tile_kernel(Jobs J, uint8_t *b
         J.copy_steps(block, jb, j, w);
         // the job form's checkpoints: byte 8 w is byte 64 (w / 8) and 8 w < n, so the place is one of the table's (n + 63) / 64
         if (jb.addr && pm_addrs::owns_checkpoint(w)) addr_table(block, jb)[w >> 3] = jb.addr[8 * w];
-        if (jb.ckpt) {
+        if (jb.ckpt || Jobs::kPieces) {
             uint64_t lo = 0, hi = 0;
             J.load_steps(j, w, &lo, &hi);
-            steps_sum = pm_addrs::lane_sum(lo, hi, w, n);
+            steps_sum = Jobs::lane_sum(lo, hi, w, n);
         }
     }
     if (threadIdx.x == 0) {
@@ -377,13 +444,13 @@ __global__ __launch_bounds__(64) void bitscan_combine_kernel(Jobs J, uint8_t *bl
             if (l == lane) mine = c;
         }
         if (r0 + lane < nt) carries[t0 + r0 + lane] = mine;
-        if (ckpt) {
+        if (ckpt || Jobs::kPieces) {
             int64_t mine_steps = 0;
             for (int l = 0; l < 64 && r0 + l < nt; ++l) {
                 if (l == lane) mine_steps = steps;
                 steps += (int64_t)__shfl(s.steps, l);
             }
-            if (r0 + lane < nt) steps_before[t0 + r0 + lane] = mine_steps;
+            if (ckpt && r0 + lane < nt) steps_before[t0 + r0 + lane] = mine_steps;
         }
     }
     if (lane == 0) {
@@ -404,7 +471,7 @@ __global__ __launch_bounds__(64) void bitscan_combine_kernel(Jobs J, uint8_t *bl
             // the carry-in into the carry piece, behind everything else of the part, and into scratch for the launches behind this one;
             // then the carry-out.  This lane is d_carry's only writer, and the tile launch has finished.
             const pm_scan_carry cin = *jb.carry;
-            int64_t *piece = reinterpret_cast<int64_t *>(rec + pm_rows::scan_bytes(kind, jb.ev0 >= 0, jb.pk0 >= 0, n, jb.addr != nullptr));
+            int64_t *piece = reinterpret_cast<int64_t *>(rec + pm_rows::scan_bytes(kind, jb.ev0 >= 0, jb.pk0 >= 0, n, jb.addr != nullptr || jb.ckpt));
             piece[0] = (int64_t)(((uint64_t)(uint32_t)cin.ones << 32) | (uint32_t)cin.state);
             piece[1] = cin.counted;
             piece[2] = cin.pieces;
@@ -422,6 +489,7 @@ __global__ __launch_bounds__(64) void bitscan_combine_kernel(Jobs J, uint8_t *bl
             out.pieces = cin.pieces + 1;
             out.bytes = cin.bytes + n;
             *jb.carry = out;
+            J.piece_end(j, piece, n, steps);
         }
     }
 }
@@ -818,7 +886,8 @@ __global__ __launch_bounds__(64) void bitscan_blocks_kernel(Jobs J, uint8_t *blo
 // launch.  The lanes load their eight steps again, one scan over the lanes gives each the steps of the tile's lanes in front, and the lane of
 // every eighth word stores A[w / 8] = the row's first address + the combine's prefix for the tile + that + the step to its own first byte
 // (pm_bitscan_addrs.h).  Every tile of every kind, behind a bail too; the emit launch covers neither.
-__global__ __launch_bounds__(kLanes) void rows_addrs_kernel(RowJobs J, uint8_t *block, const int64_t *steps_before)
+template <class Jobs>
+__global__ __launch_bounds__(kLanes) void rows_addrs_kernel(Jobs J, uint8_t *block, const int64_t *steps_before)
 {
     __shared__ uint32_t lds[kLanes];
     const int tile = blockIdx.x, tw = J.tile_words;
@@ -831,11 +900,11 @@ __global__ __launch_bounds__(kLanes) void rows_addrs_kernel(RowJobs J, uint8_t *
     const bool active = (int)threadIdx.x < tw && w < nw;
     uint64_t lo = 0, hi = 0;
     if (active) J.load_steps(j, w, &lo, &hi);
-    block_scan(active ? pm_addrs::lane_sum(lo, hi, w, n) : 0u, lds, [](uint32_t a, uint32_t b) { return a + b; });
+    block_scan(active ? Jobs::lane_sum(lo, hi, w, n) : 0u, lds, [](uint32_t a, uint32_t b) { return a + b; });
     const uint32_t before = threadIdx.x ? lds[threadIdx.x - 1] : 0u;
     // (8 w < n: the place is one of the table's (n + 63) / 64)
     if (active && pm_addrs::owns_checkpoint(w))
-        addr_table(block, jb)[w >> 3] = pm_addrs::checkpoint(J.recs[J.row0 + j].first_addr, steps_before[tile], before, pm_addrs::lane_first(lo, w));
+        addr_table(block, jb)[w >> 3] = pm_addrs::checkpoint(J.addr_before(j), steps_before[tile], before, Jobs::lane_first(lo, w));
 }
 
 // The prepare launch of pm_rows_scan: the row table from the records' counts and the chains' kinds (pm_bitscan_rows.h) -- one workgroup,
@@ -861,6 +930,56 @@ __global__ __launch_bounds__(kLanes) void rows_prepare_kernel(RowJobs J, const p
     if (threadIdx.x == 0) table[J.nrows] = total_entry(carry, limit);
 }
 
+// The prepare launch of pm_rows_scan_pieces: the same trips, with each row's piece cut from its record's count, the caller's `upto` and its
+// carry's `taken` (pm_rows::piece_bytes), and the address in front of the piece from the record or the carry.
+__global__ __launch_bounds__(kLanes) void rows_pieces_prepare_kernel(RowPieceJobs J, const pm_rowslice_rec *recs, const int64_t *upto, int32_t final_piece,
+                                                                     pm_rows::PieceEntry *table, pm_rows::Sums limit)
+{
+    using namespace pm_rows;
+    __shared__ Sums lds[kLanes];
+    Sums carry = sums_zero();
+    for (int r0 = 0; r0 < J.nrows; r0 += kTrip) {
+        const int r = r0 + (int)threadIdx.x, c = (int)((J.row0 + r) % J.nchains);
+        const bool active = r < J.nrows;
+        int64_t n = 0, from = 0, addr_before = 0;
+        if (active) {
+            const pm_rowslice_rec *q = recs + J.row0 + r;
+            const pm_rows_carry *cy = J.carries + J.row0 + r;
+            from = cy->taken;
+            n = piece_bytes(piece_avail(q->count, J.cap, upto != nullptr, upto ? upto[r] : 0), from, final_piece != 0);
+            addr_before = from ? cy->last_addr : q->first_addr;
+        }
+        const Sums mine = active ? piece_sums(J.kind[c], J.frames[c], J.packets[c], n < kMaxBytes ? n : kMaxBytes, J.tile_words, J.addrs[c]) : sums_zero();
+        block_scan(mine, lds, [](const Sums &a, const Sums &b) { return sums_add(a, b); });
+        const Sums before = sums_add(carry, threadIdx.x ? lds[threadIdx.x - 1] : sums_zero());
+        carry = sums_add(carry, lds[kLanes - 1]);
+        if (active) table[r] = piece_entry(before, J.kind[c], J.frames[c], J.packets[c], n, J.tile_words, limit, J.addrs[c], from, addr_before);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) table[J.nrows] = piece_total_entry(carry, limit);
+}
+
+// pm_rows_carry_start: a lane a row
+struct ChainRegs {
+    uint64_t reg0[pm_rows::kMaxChains];
+};
+__global__ __launch_bounds__(kLanes) void rows_carry_start_kernel(pm_rows_carry *carries, int64_t row0, int nrows, ChainRegs regs, int nchains)
+{
+    const int r = (int)(blockIdx.x * kLanes + threadIdx.x);
+    if (r >= nrows) return;
+    pm_rows_carry v;
+    v.scan.lfsr_state = regs.reg0[(row0 + r) % nchains];
+    v.scan.tail = 0;
+    v.scan.counted = 0;
+    v.scan.pieces = 0;
+    v.scan.bytes = 0;
+    v.scan.ones = 0;
+    v.scan.state = PM_SCAN_CARRY_START;
+    v.taken = 0;
+    v.last_addr = 0;
+    carries[row0 + r] = v;
+}
+
 // what the launches share in context scratch, cut for `jobs` jobs (or rows)
 struct ScanScratch {
     TileSum *sums;
@@ -872,10 +991,10 @@ struct ScanScratch {
     PkRec *recs;
     uint8_t *extra;                         // `extra_bytes` behind everything, 64-byte aligned (the row table)
     int64_t *steps_before;                  // the row form's addrs: per tile the steps of its row's tiles in front, nullptr: no checkpoints
-    pm_scan_carry *carry_in;                // the job form's carries as the jobs found them (kScanJobs of them), nullptr: the row form
+    pm_scan_carry *carry_in;                // the carries as the jobs (or the rows' pieces) found them, one per job, nullptr: none is carried
 };
 int scan_scratch(pm_ctx *ctx, size_t jobs, int64_t tiles, int64_t copies, int64_t places, size_t extra_bytes, ScanScratch *out, bool steps_before = false,
-                 bool carries = false)
+                 size_t carries = 0)
 {
     const size_t sums_bytes = ((size_t)tiles * sizeof(TileSum) + 63) & ~(size_t)63;
     // (frames: the event counts and a copy of the lists stay on the device for the frames launch, behind the carries)
@@ -884,7 +1003,7 @@ int scan_scratch(pm_ctx *ctx, size_t jobs, int64_t tiles, int64_t copies, int64_
     const size_t lists_bytes = (size_t)copies * sizeof(uint2), cands_bytes = ((size_t)places * sizeof(uint32_t) + 63) & ~(size_t)63, recs_bytes = (size_t)places * sizeof(PkRec);
     const size_t pk_bytes = places ? 2 * cands_bytes + recs_bytes + 2 * jobs * sizeof(int32_t) : 0;
     const size_t extra_padded = (extra_bytes + 63) & ~(size_t)63, before_bytes = steps_before ? (size_t)tiles * sizeof(int64_t) : 0;
-    const size_t carry_bytes = carries ? kScanJobs * sizeof(pm_scan_carry) : 0;
+    const size_t carry_bytes = carries * sizeof(pm_scan_carry);
     if (int rc = pm_scratch_reserve(ctx, sums_bytes + carries_bytes + counts_bytes + lists_bytes + pk_bytes + extra_padded + before_bytes + carry_bytes + 256)) return rc;
     uint8_t *base = static_cast<uint8_t *>(ctx->d_scratch);
     out->sums = reinterpret_cast<TileSum *>(base);
@@ -1004,7 +1123,7 @@ extern "C" int pm_stream_scan(pm_ctx *ctx, const pm_scan_job *h_jobs, int njobs,
     *h_used = at;
     if (at > block_bytes) return pm_set_error(PM_ERR_CAPACITY, "pm_stream_scan: the block holds %zu bytes, the batch needs %zu", block_bytes, at);
     ScanScratch s;
-    if (int rc = scan_scratch(ctx, kScanJobs, tiles, copies, places, 0, &s, false, any_carry)) return rc;
+    if (int rc = scan_scratch(ctx, kScanJobs, tiles, copies, places, 0, &s, false, any_carry ? kScanJobs : 0)) return rc;
     ScanJobs L = J;                                         // behind the combine launch the carries are read from its copies
     L.carry_in = s.carry_in;
     L.late = 1;
@@ -1015,17 +1134,14 @@ extern "C" int pm_stream_scan(pm_ctx *ctx, const pm_scan_job *h_jobs, int njobs,
     return PM_OK;
 }
 
-extern "C" int pm_rows_scan(pm_ctx *ctx, const pm_rowslice_rec *d_recs, const uint8_t *d_data, const uint16_t *d_steps, int64_t cap, int64_t row0, int nrows,
-                            const pm_rows_scan_chain *h_chains, int nchains, const int64_t *h_counts, void *d_block, size_t block_bytes, int64_t *h_offsets,
-                            size_t *h_used)
+// what pm_rows_scan and pm_rows_scan_pieces share: the arguments' checks and the table's fields that do not depend on the rows
+static int rows_jobs_fill(pm_ctx *ctx, RowJobs &J, const pm_rowslice_rec *d_recs, const uint8_t *d_data, const uint16_t *d_steps, int64_t cap, int64_t row0, int nrows,
+                          const pm_rows_scan_chain *h_chains, int nchains, const int64_t *h_counts, void *d_block, int64_t *h_offsets, size_t *h_used)
 {
     using namespace pm_rows;
-    PM_CTX(ctx);
     PM_ARG(d_recs && d_data && d_steps && cap >= 0 && (cap & 7) == 0 && ((uintptr_t)d_data & 7) == 0 && ((uintptr_t)d_steps & 7) == 0 && row0 >= 0);
     PM_ARG(nrows >= 1 && nrows <= kMaxRows && h_chains && nchains >= 1 && nchains <= kMaxChains && h_counts);
     PM_ARG(d_block && ((uintptr_t)d_block & 7) == 0 && h_offsets && h_used);
-    RowJobs J;
-    memset(&J, 0, sizeof(J));
     J.data = d_data;
     J.steps = d_steps;
     J.recs = d_recs;
@@ -1054,6 +1170,18 @@ extern "C" int pm_rows_scan(pm_ctx *ctx, const pm_rowslice_rec *d_recs, const ui
         // (a min_dist below 0 corrects what 0 does, one above 8 nothing: the locator has eight roots at most)
         J.pkopt[c] = (uint8_t)((q.il2p_crc != 0) | (q.il2p_disable_rs != 0) << 1 | std::max(0, std::min(9, q.il2p_min_dist)) << 2);
     }
+    return PM_OK;
+}
+
+extern "C" int pm_rows_scan(pm_ctx *ctx, const pm_rowslice_rec *d_recs, const uint8_t *d_data, const uint16_t *d_steps, int64_t cap, int64_t row0, int nrows,
+                            const pm_rows_scan_chain *h_chains, int nchains, const int64_t *h_counts, void *d_block, size_t block_bytes, int64_t *h_offsets,
+                            size_t *h_used)
+{
+    using namespace pm_rows;
+    PM_CTX(ctx);
+    RowJobs J;
+    memset(&J, 0, sizeof(J));
+    if (int rc = rows_jobs_fill(ctx, J, d_recs, d_data, d_steps, cap, row0, nrows, h_chains, nchains, h_counts, d_block, h_offsets, h_used)) return rc;
     // the host's copy of the sums, for the sizes: the device makes its own from the records
     Sums all = sums_zero();
     bool any = false, any_addrs = false;
@@ -1076,7 +1204,61 @@ extern "C" int pm_rows_scan(pm_ctx *ctx, const pm_rowslice_rec *d_recs, const ui
     hipLaunchKernelGGL(rows_prepare_kernel, dim3(1), dim3(kLanes), 0, ctx->stream, J, d_recs, table, all);
     scan_launch(ctx, J, J, nrows, all.tiles, all.events, all.places, any, static_cast<uint8_t *>(d_block), s, kRowFrameWaves, kRowPacketWaves);
     if (any_addrs && all.tiles)
-        hipLaunchKernelGGL(rows_addrs_kernel, dim3((unsigned)all.tiles), dim3(kLanes), 0, ctx->stream, J, static_cast<uint8_t *>(d_block), s.steps_before);
+        hipLaunchKernelGGL(rows_addrs_kernel<RowJobs>, dim3((unsigned)all.tiles), dim3(kLanes), 0, ctx->stream, J, static_cast<uint8_t *>(d_block), s.steps_before);
+    PM_HIP(hipGetLastError());
+    return PM_OK;
+}
+
+extern "C" int pm_rows_carry_start(pm_ctx *ctx, pm_rows_carry *d_carries, int64_t row0, int nrows, const pm_rows_scan_chain *h_chains, int nchains)
+{
+    PM_CTX(ctx);
+    PM_ARG(d_carries && ((uintptr_t)d_carries & 7) == 0 && row0 >= 0 && nrows >= 1 && h_chains && nchains >= 1 && nchains <= pm_rows::kMaxChains);
+    ChainRegs regs;
+    memset(&regs, 0, sizeof(regs));
+    for (int c = 0; c < nchains; ++c) regs.reg0[c] = h_chains[c].lfsr_state;
+    hipLaunchKernelGGL(rows_carry_start_kernel, dim3((unsigned)pm_cdiv(nrows, kLanes)), dim3(kLanes), 0, ctx->stream, d_carries, row0, nrows, regs, nchains);
+    PM_HIP(hipGetLastError());
+    return PM_OK;
+}
+
+extern "C" int pm_rows_scan_pieces(pm_ctx *ctx, const pm_rowslice_rec *d_recs, const uint8_t *d_data, const uint16_t *d_steps, int64_t cap, int64_t row0, int nrows,
+                                   const pm_rows_scan_chain *h_chains, int nchains, pm_rows_carry *d_carries, const int64_t *d_upto, int32_t final_piece,
+                                   const int64_t *h_counts, void *d_block, size_t block_bytes, int64_t *h_offsets, size_t *h_used)
+{
+    using namespace pm_rows;
+    PM_CTX(ctx);
+    RowPieceJobs J;
+    memset(&J, 0, sizeof(J));
+    if (int rc = rows_jobs_fill(ctx, J, d_recs, d_data, d_steps, cap, row0, nrows, h_chains, nchains, h_counts, d_block, h_offsets, h_used)) return rc;
+    PM_ARG(d_carries && ((uintptr_t)d_carries & 7) == 0 && ((uintptr_t)d_upto & 7) == 0);
+    J.carries = d_carries;
+    // the host's copy of the sums, for the sizes: the device cuts the pieces itself, from the records, d_upto and the carries
+    Sums all = sums_zero();
+    bool any = false, any_addrs = false;
+    for (int r = 0; r < nrows; ++r) {
+        const pm_rows_scan_chain &q = h_chains[(row0 + r) % nchains];
+        any_addrs = any_addrs || q.addrs;
+        const int64_t n = h_counts[r];
+        PM_ARG(n >= 0 && n <= cap && n <= kMaxBytes);
+        h_offsets[r] = all.off;
+        all = sums_add(all, piece_sums(q.codec_kind, q.frames, q.packets, n, J.tile_words, q.addrs));
+        PM_ARG(all.tiles < (int64_t)1 << 30);
+        any = any || ((q.codec_kind == 0 || q.packets) && n > 0);
+    }
+    *h_used = (size_t)all.off;
+    if ((size_t)all.off > block_bytes)
+        return pm_set_error(PM_ERR_CAPACITY, "pm_rows_scan_pieces: the block holds %zu bytes, the pieces need %zu", block_bytes, (size_t)all.off);
+    ScanScratch s;
+    if (int rc = scan_scratch(ctx, (size_t)nrows, all.tiles, all.events, all.places, ((size_t)nrows + 1) * sizeof(PieceEntry), &s, any_addrs, (size_t)nrows)) return rc;
+    PieceEntry *table = reinterpret_cast<PieceEntry *>(s.extra);
+    J.ptable = table;
+    RowPieceJobs L = J;                                     // behind the combine launch the carries are read from its copies
+    L.carry_in = s.carry_in;
+    L.late = 1;
+    hipLaunchKernelGGL(rows_pieces_prepare_kernel, dim3(1), dim3(kLanes), 0, ctx->stream, J, d_recs, d_upto, final_piece, table, all);
+    scan_launch(ctx, J, L, nrows, all.tiles, all.events, all.places, any, static_cast<uint8_t *>(d_block), s, kRowFrameWaves, kRowPacketWaves);
+    if (any_addrs && all.tiles)
+        hipLaunchKernelGGL(rows_addrs_kernel<RowPieceJobs>, dim3((unsigned)all.tiles), dim3(kLanes), 0, ctx->stream, L, static_cast<uint8_t *>(d_block), s.steps_before);
     PM_HIP(hipGetLastError());
     return PM_OK;
 }

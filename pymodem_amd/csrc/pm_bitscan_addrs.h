@@ -6,6 +6,7 @@
 // by lane and tile by tile against a plain prefix sum.
 //   address of byte k = first + steps[1] + ... + steps[k]          (steps[0], "the first one 0", is never added)
 //   A[w]              = address of byte 64 w
+// A piece of a row (pm_rows_scan_pieces) counts from the address in front of it, its step 0 included: piece_lane_sum, piece_lane_first.
 // A lane's sum fits 32 bits (8 x 65535), a tile's does at 256 words (2048 x 65535 < 2^28); a stream's does not.
 #pragma once
 #include <cstdint>
@@ -46,6 +47,18 @@ PM_AD_HD int64_t checkpoint(int64_t first, int64_t tiles_before, uint32_t lanes_
 {
     return first + tiles_before + (int64_t)lanes_before + (int64_t)own_first;
 }
+
+// ---- a PIECE of a row (pm_rows_scan_pieces): the address in front of the piece is that of the byte before it, so the piece's step 0 counts:
+//   address of the piece's byte k = addr_before + steps[0] + ... + steps[k],   A[w] = address of its byte 64 w
+// (checkpoint() above with addr_before for `first`, these sums and this first step)
+PM_AD_HD uint32_t piece_lane_sum(uint64_t lo, uint64_t hi, int64_t w, int64_t n)
+{
+    uint32_t s = 0;
+    for (int i = 0; i < 8; ++i)
+        if (8 * w + i < n) s += step_of(lo, hi, i);
+    return s;
+}
+PM_AD_HD uint32_t piece_lane_first(uint64_t lo) { return (uint32_t)(lo & 0xFFFFu); }
 
 // ---- the host's side --------------------------------------------------------------------------------------------------------------------
 // One stream's table and steps; [k]: the address of byte k.  Counts what it did (pm_codec_addr_work).

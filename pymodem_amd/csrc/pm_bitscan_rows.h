@@ -3,6 +3,8 @@
 // in the candidate, record and work lists -- the entry of the device-side row table that the prepare launch makes from them, and the search
 // for a tile's row.  Free of loads, LDS and launches, so that the same text runs on the host: the prepare kernel, the launcher and
 // tests/rows_scan_core_check.cpp (which steps the prepare launch's trips of 256 rows against a plain prefix sum) all go by it.
+// At the end: the same for rows taken in PIECES (pm_rows_scan_pieces) -- how a piece is cut, its part's size, its own table entry
+// (tests/rows_pieces_core_check.cpp).
 #pragma once
 #include <cstdint>
 
@@ -89,6 +91,51 @@ PM_ROWS_HD int row_of_tile(Tile0 tile0, int nrows, int tile)
         else hi = mid - 1;
     }
     return lo;
+}
+
+// ---- rows in PIECES (pm_rows_scan_pieces) -------------------------------------------------------------------------------------------------
+// A row is taken piece by piece: `taken` bytes have gone (pm_rows_carry.taken), the next piece begins there.  All but the final cut are
+// multiples of 8, so that every piece's bytes and steps stay 8-byte aligned in their row (cap is a multiple of 8); a row whose `taken` is no
+// multiple of 8 has had its final piece and gives empty pieces from then on.
+constexpr int kPieceTail = 40;              // PM_ROWS_PIECE_TAIL_BYTES: the job form's carry piece (32) and int64 addr_before, last in the part
+
+// what the row holds for this piece: the caller's `upto`, if it gave one, within the record's count and the row's room
+PM_ROWS_HD int64_t piece_avail(int64_t count, int64_t cap, bool has_upto, int64_t upto)
+{
+    const int64_t room = row_bytes(count, cap);
+    return has_upto && upto < room ? upto : room;
+}
+// the piece's bytes
+PM_ROWS_HD int64_t piece_bytes(int64_t avail, int64_t taken, bool final)
+{
+    if (taken & 7) return 0;                // the final piece has gone
+    int64_t n = avail - taken;
+    if (!final) n &= ~(int64_t)7;           // (rounds down, below zero too)
+    return n < 0 ? 0 : n;
+}
+PM_ROWS_HD int64_t piece_part_bytes(int kind, int frames, int packets, int64_t n, int addrs = 0) { return part_bytes(kind, frames, packets, n, addrs) + kPieceTail; }
+PM_ROWS_HD Sums piece_sums(int kind, int frames, int packets, int64_t n, int tile_words, int addrs = 0)
+{
+    return Sums{piece_part_bytes(kind, frames, packets, n, addrs), row_tiles(n, tile_words), row_events(frames, n), row_places(packets, n)};
+}
+// A piece's row of the device-side table: Entry's fields, where in its row the piece begins, and the address in front of its first step.
+struct PieceEntry {
+    int64_t off, ev0, pk0;
+    int32_t n, tile0;
+    int64_t from;                           // bytes of the row in front of the piece: its bytes lie at row * cap + from, its steps likewise
+    int64_t addr_before;                    // the stream address of byte from - 1 (the row's first address while from == 0, where the first step is 0)
+};
+PM_ROWS_HD PieceEntry piece_entry(const Sums &before, int kind, int frames, int packets, int64_t n, int tile_words, const Sums &limit, int addrs, int64_t from,
+                                  int64_t addr_before)
+{
+    const Sums end = sums_add(before, piece_sums(kind, frames, packets, n < kMaxBytes ? n : kMaxBytes, tile_words, addrs));
+    const bool ok = n <= kMaxBytes && end.off <= limit.off && end.tiles <= limit.tiles && end.events <= limit.events && end.places <= limit.places;
+    return PieceEntry{ok ? before.off : -1, frames ? before.events : -1, packets ? before.places : -1, (int32_t)(n < kMaxBytes ? n : kMaxBytes),
+                      (int32_t)(before.tiles < limit.tiles ? before.tiles : limit.tiles), from, addr_before};
+}
+PM_ROWS_HD PieceEntry piece_total_entry(const Sums &all, const Sums &limit)
+{
+    return PieceEntry{all.off, -1, -1, 0, (int32_t)(all.tiles < limit.tiles ? all.tiles : limit.tiles), 0, 0};
 }
 
 }  // namespace pm_rows

@@ -1304,7 +1304,8 @@ int pm_codec_decode_carried(pm_codec *c, const uint8_t *h_plain, const int64_t *
     }
     bool ok;
     if (addrs) {
-        if (!pm_addrs::table_fits(ckpt, n, addr_first))
+        // (a piece of a row begins behind addr_first: its step 0, which a whole stream has as 0, leads to byte 0 -- pm_rows_scan_pieces)
+        if (!pm_addrs::table_fits(ckpt, n, addr_first + (n > 0 ? (int64_t)h_steps[0] : 0)))
             return pm_set_error(PM_ERR_ARG, "pm_codec_decode_carried: the checkpoint table does not belong to a stream of %lld bytes that begins at address %lld",
                                 (long long)n, (long long)addr_first);
         pm_addrs::Lookup look{ckpt, h_steps, 0, 0};

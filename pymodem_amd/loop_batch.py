@@ -308,6 +308,109 @@ class SlicedRun:
             out.append((host[o:o + 2 * c].view(np.uint16), int(recs["first_addr"][k]), c, host[o + sw:o + sw + parts[k]]))
         return out
 
+    def pieces(self, chains, frames=False, packets=False, addrs=False):
+        """The rows of this run scanned piece by piece (pm_rows_scan_pieces), a device carry per row: -> RowPieces.  `chains`, frames, packets
+        and addrs as for fetch_scanned()."""
+        return RowPieces(self, chains, frames, packets, addrs)
+
+
+class RowPieces:
+    """A sliced run's rows taken in pieces with the bitstream stage on the device: owns the rows' carries (pm_rows_carry, 64 bytes a row, started
+    with pm_rows_carry_start in front of a row's first piece, on the stream that takes it) and the host's shadow of `taken` per row.  The
+    pieces of a row must be fetched through one context (copy_ctx), one after the other; every piece is to be decoded (chain_execute.
+    _host_rows_pieces) before the row's next one is fetched, and the rows that it names are to be seeded again (seed()).  seeds, ordinary: how
+    often a carry was seeded from a codec's registers behind a bail, and how many pieces went the ordinary way."""
+
+    def __init__(self, run, chains, frames=False, packets=False, addrs=False):
+        self.run, self.chains, self.frames, self.packets, self.addrs = run, chains, bool(frames), bool(packets), bool(addrs)
+        nchains = len(chains)
+        self.desc = (N.RowsScanChain * nchains)()
+        for d, ch in zip(self.desc, chains):
+            lfsr, codec = ch[3], ch[4]
+            d.lfsr_poly, d.lfsr_state, d.lfsr_invert = lfsr.polynomial, lfsr.shift_register, int(bool(lfsr.invert))
+            d.codec_kind, d.sync_tol = int(codec._kind), int(codec.sync_tolerance)
+            d.frames, d.packets = int(self.frames and codec._kind == 0), int(self.packets and codec._kind == 1)
+            d.il2p_crc, d.il2p_disable_rs, d.il2p_min_dist = int(codec.collect_trailing_crc), int(codec.disable_rs), int(codec.min_distance)
+            d.addrs = int(self.addrs)
+        self.carries = run.ctx.empty(run.rows * ctypes.sizeof(N.RowsCarry), np.uint8)
+        self.taken = np.zeros(run.rows, dtype=np.int64)      # the host's shadow of pm_rows_carry.taken
+        self.begun = np.zeros(run.rows, dtype=bool)
+        self.last_from = np.zeros(run.rows, dtype=np.int64)  # where each row's last piece began
+        self.seeds = self.ordinary = 0
+        self._lock = threading.Lock()
+
+    def piece_bytes(self, row0, nrows, upto=None, final=False):
+        """n of the next piece of every row, by pm_rows_scan_pieces' rule, from the records and the shadow of `taken`"""
+        recs = self.run.records()[row0:row0 + nrows]
+        taken = self.taken[row0:row0 + nrows]
+        avail = np.clip(recs["count"], 0, self.run.cap)
+        if upto is not None:
+            avail = np.minimum(avail, np.asarray(upto, dtype=np.int64))
+        n = avail - taken
+        if not final:
+            n = n // 8 * 8                                   # (floor: rounds down below zero too)
+        return np.ascontiguousarray(np.where(taken % 8 != 0, 0, np.maximum(n, 0)), dtype=np.int64)
+
+    def fetch(self, row0, nrows, upto=None, final=False, copy_ctx=None, tag=None):
+        """The next piece of rows row0 .. row0 + nrows - 1: up to `upto` bytes of each row (an int64 per row, None: the records' counts), cut at
+        a multiple of 8 unless `final`.  -> per row (the piece's address steps, addr_before, n, the piece's scan part with its carry piece) as
+        views of one host block: the upload of `upto`, one pm_rows_scan_pieces and ONE copy to the host for the lot."""
+        run = self.run
+        ctx = copy_ctx or run.ctx
+        nchains = len(self.chains)
+        if not self.begun[row0:row0 + nrows].all():
+            check(lib().pm_rows_carry_start(ctx.handle, self.carries.ptr, row0, nrows, self.desc, nchains))
+            self.begun[row0:row0 + nrows] = True
+        counts = self.piece_bytes(row0, nrows, upto, final)
+        key = tag if tag is not None else ("sliced-run", id(run))
+        d_upto = None
+        if upto is not None:
+            h_upto = np.ascontiguousarray(upto, dtype=np.int64)
+            assert len(h_upto) == nrows
+            d_upto = ctx.scratch((key, "upto"), nrows, np.int64)
+            check(lib().pm_h2d(ctx.handle, d_upto.ptr, h_upto.ctypes.data_as(ctypes.c_void_p), h_upto.nbytes))
+        of = [self.desc[(row0 + k) % nchains] for k in range(nrows)]
+        sizes = [N.rows_piece_part_bytes(d.codec_kind, d.frames, d.packets, int(c), d.addrs) for d, c in zip(of, counts)]
+        used = int(sum(sizes))
+        # (the same 8 MB size classes as fetch_scanned())
+        room = (used + (8 << 20) - 1) // (8 << 20) * (8 << 20)
+        block = ctx.scratch((key, "pieces"), room, np.uint8)
+        offs, need = (ctypes.c_int64 * nrows)(), ctypes.c_size_t()
+        check(lib().pm_rows_scan_pieces(ctx.handle, run.recs.ptr, run.data.ptr, run.steps.ptr, run.cap, row0, nrows, self.desc, nchains, self.carries.ptr,
+                                        d_upto.ptr if d_upto is not None else None, int(bool(final)), counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                        block.ptr, block.n, offs, ctypes.byref(need)))
+        assert need.value == used, "pm_rows_scan_pieces and _native.rows_piece_part_bytes size a piece alike"
+        host = block.download(used, recycle=True, ctx=ctx, room=room)
+        with run._copied_lock:
+            run.copied += used
+        self.last_from[row0:row0 + nrows] = self.taken[row0:row0 + nrows]
+        self.taken[row0:row0 + nrows] += counts
+        out = []
+        for k in range(nrows):
+            c, o = int(counts[k]), int(offs[k])
+            sw, end = N.rows_scan_steps_bytes(c), o + sizes[k]
+            out.append((host[o:o + 2 * c].view(np.uint16), int(host[end - 8:end].view(np.int64)[0]), c, host[o + sw:end - 8]))
+        return out
+
+    def raw(self, row, copy_ctx=None, tag=None):
+        """the slicer bytes of the row's last piece, for a piece that goes the ordinary way (SlicedRun.fetch brings the row)"""
+        from .data_classes import AddressedArray
+        whole = self.run.fetch(row, 1, copy_ctx, tag)[0]
+        a, b = int(self.last_from[row]), int(self.taken[row])
+        return AddressedArray(np.ascontiguousarray(whole.data[a:b]), np.ascontiguousarray(whole.address[a:b]))
+
+    def seed(self, row, lfsr_state, ones, counted, copy_ctx=None):
+        """pm_scan_carry_set on the row's carry from its codec's registers (pm_codec_scan_state) and its LFSR's, behind a piece that bailed or
+        went the ordinary way: `taken` and `last_addr` stay."""
+        ctx = copy_ctx or self.run.ctx
+        check(lib().pm_scan_carry_set(ctx.handle, self.carries.ptr.value + row * ctypes.sizeof(N.RowsCarry), int(lfsr_state), int(ones), int(counted)))
+        with self._lock:
+            self.seeds += 1
+
+    def went_ordinary(self, count):
+        with self._lock:
+            self.ordinary += int(count)
+
 
 
 _ENGINES = {}
@@ -349,7 +452,7 @@ def _scannable(chain_sets):
 
 
 def process_recordings_device(chain_sets, audios, ctx=None, chunk=0, rows=False, chain_ids=None, stages=None, slot=0, defer=False, scan=None,
-                              frames=None, packets=None, addrs=None):
+                              frames=None, packets=None, addrs=None, pieces=None):
     """chain_sets[k] = the chains [name, modem, slicer, stream, codec] of recording k (every recording brings the same group of
     chains, as a service decoding successive recordings with one config does), audios[k] its int16 samples (host array or
     DeviceBuffer; equal lengths).  -> [[packets of chain 0, ...] per recording], identical to chain_execute.process_chain on each
@@ -362,8 +465,13 @@ def process_recordings_device(chain_sets, audios, ctx=None, chunk=0, rows=False,
     pm_rows_scan (SlicedRun.fetch_scanned), and the codecs decode from its lists -- with frames the AX.25 chains' frames, with packets the
     IL2P chains' headers and RS blocks come from there too.  addrs (None: the context's switch pipe_addrs, PM_PIPE_ADDRS; implies scan): the
     rows bring address checkpoints and the codecs resolve an address where they need one instead of expanding every step.  Results are the
-    same; stages["scanned"] says which way the decode went."""
-    from .chain_execute import _host_rows, _host_rows_scanned, _host_stages, _host_stages_scanned, _pool
+    same; stages["scanned"] says which way the decode went.
+    pieces (an integer k >= 2; the fused-slicer route with the scan on and chains it can describe, ignored otherwise -- stages["pieces"] is
+    then False): every group of rows is taken in k pieces through RowPieces -- up to count * p // k bytes of each row for p = 1 .. k - 1, then
+    the final piece -- and each piece is decoded by the carried host route before the next piece of the same rows is fetched, as an engine
+    that hands over its rows per time chunk would drive it.  Results are the same, nothing is faster; stages["pieces"] = {"pieces": k,
+    "seeds": carries seeded again behind a bail, "ordinary": pieces that went the ordinary way}."""
+    from .chain_execute import _host_rows, _host_rows_pieces, _host_rows_scanned, _host_stages, _host_stages_scanned, _pool
     from .slicer import slice_batch
     ctx = ctx or Context.default()
     r = len(chain_sets)
@@ -373,6 +481,8 @@ def process_recordings_device(chain_sets, audios, ctx=None, chunk=0, rows=False,
     packets = bool(ctx.tuned("pipe_packets")) if packets is None else bool(packets)
     addrs = bool(ctx.tuned("pipe_addrs")) if addrs is None else bool(addrs)
     scan = (bool(ctx.tuned("pipe_scan")) if scan is None else bool(scan)) or frames or packets or addrs
+    if pieces is not None and (int(pieces) != pieces or pieces < 2):
+        raise ValueError("process_recordings_device: pieces is an integer >= 2")
     dev = []
     for a in audios:
         if isinstance(a, DeviceBuffer):
@@ -411,6 +521,7 @@ def process_recordings_device(chain_sets, audios, ctx=None, chunk=0, rows=False,
         run.records(Context.side(ctx.device, 399))          # (not on the context's own stream: the next run may be queued on it by now)
         if run.ok():
             scanned = scan and _scannable(chain_sets)       # (foreign stream or codec objects, or codecs that have been used, go the old way)
+            in_pieces = int(pieces) if scanned and pieces is not None else 0
 
             def rest():
                 for rec in range(r):
@@ -425,11 +536,40 @@ def process_recordings_device(chain_sets, audios, ctx=None, chunk=0, rows=False,
                 cuts = [r * p // parts for p in range(parts + 1)]
                 sides = [Context.side(ctx.device, 400 + p) for p in range(parts)]
                 early = {}
+                taker = run.pieces(chain_sets[0], frames, packets, addrs) if in_pieces else None
+
+                def part_in_pieces(p, lo, hi):
+                    # every piece of these rows is decoded, and the carries that it names are seeded again, before the next one is fetched
+                    from concurrent.futures import Future
+                    from .packet_meta import rows_to_packets
+                    row0, nr = lo * nchains, (hi - lo) * nchains
+                    counts = np.asarray(run.records()["count"][row0:row0 + nr], dtype=np.int64)
+                    got_rows = {rec: [[] for _ in range(nchains)] for rec in range(lo, hi)}
+                    for q in range(1, in_pieces + 1):
+                        final = q == in_pieces
+                        got = taker.fetch(row0, nr, None if final else counts * q // in_pieces, final, sides[p], tag=("loop-sliced", p))
+                        for rec in range(lo, hi):
+                            views, again, ordinary = _host_rows_pieces(chain_sets[rec], got[(rec - lo) * nchains:(rec - lo + 1) * nchains], chain_ids, frames, packets,
+                                                                       addrs, lambda j, rec=rec: taker.raw(rec * nchains + j, sides[p], ("loop-sliced", p)))
+                            for c, v in enumerate(views):
+                                got_rows[rec][c].append(v)
+                            taker.went_ordinary(ordinary)
+                            for j, reg, ones, counted in again:
+                                taker.seed(rec * nchains + j, reg, ones, counted, sides[p])
+                    for rec in range(lo, hi):
+                        blocks = [np.concatenate(v) for v in got_rows[rec]]
+                        early[rec] = Future()
+                        early[rec].set_result(blocks if rows else [rows_to_packets(b, ch[4].identifier) for ch, b in zip(chain_sets[rec], blocks)])
 
                 def part(p):
                     out = []
                     for lo in range(cuts[p], cuts[p + 1], per):
                         hi = min(lo + per, cuts[p + 1])
+                        if in_pieces:
+                            part_in_pieces(p, lo, hi)
+                            if stages is not None:          # (diagnosis only: the slicers' bytes as the old way brings them)
+                                out += run.fetch(lo * nchains, (hi - lo) * nchains, sides[p], tag=("loop-sliced", p))
+                            continue
                         if scanned:
                             # the bitstream stage on the device in front of the copy; a recording's rows go to the codecs at once
                             got = run.fetch_scanned(lo * nchains, (hi - lo) * nchains, chain_sets[0], frames, packets, sides[p], tag=("loop-sliced", p),
@@ -458,6 +598,8 @@ def process_recordings_device(chain_sets, audios, ctx=None, chunk=0, rows=False,
                     stages["fused_slicers"] = True
                     stages["scanned"] = bool(scanned)
                     stages["copied_bytes"] = run.copied     # (with the scan on: the plain fetch for stages["sliced"] counted too)
+                    if pieces is not None:
+                        stages["pieces"] = {"pieces": in_pieces, "seeds": taker.seeds, "ordinary": taker.ordinary} if in_pieces else False
                 if scanned:
                     out = [early[rec].result() for rec in range(r)]
                     if stages is not None:
@@ -526,6 +668,8 @@ def process_recordings_device(chain_sets, audios, ctx=None, chunk=0, rows=False,
     if stages is not None:
         stages["sliced"] = [sliced[rec * nchains:(rec + 1) * nchains] for rec in range(r)]
         stages["seconds"] = {"engine": t1 - t0, "slicers": t2 - t1}
+        if pieces is not None:
+            stages["pieces"] = False                         # (not the fused-slicer route: ignored)
     out = []
     if rows:
         futs = [early[rec] if rec in early else _pool().submit(_host_rows, chain_sets[rec], sliced[rec * nchains:(rec + 1) * nchains], chain_ids)
