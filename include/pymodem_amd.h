@@ -45,10 +45,14 @@ int pm_device_count(void);                               /* 0 when no GPU; never
 int pm_last_error(char *buf, size_t cap);                /* copies the calling thread's last message */
 
 int pm_ctx_create(int device, pm_ctx **out);
-/* Same, with the stream at the device's highest priority when high_priority != 0.  Several ctx may exist on one device: each has
- * its own stream, scratch and profiler, device memory is shared.  The pipelined executor runs the slicer (a few resident waves,
- * dependent-latency bound) on a high-priority ctx while the FIR/correlator kernels of the next recording fill the ALUs. */
-int pm_ctx_create_prio(int device, int high_priority, pm_ctx **out);
+/* Same, with the stream at one of three priority levels: 1 the device's highest, 0 a plain stream, -1 the device's lowest (both ends
+ * from hipDeviceGetStreamPriorityRange; a device with one level gives a plain stream for all three).  Any other level: PM_ERR_ARG.
+ * Several ctx may exist on one device: each has its own stream, scratch and profiler, device memory is shared.  The pipelined executor
+ * runs the slicer (a few resident waves, dependent-latency bound) on a high-priority ctx while the FIR/correlator kernels of the next
+ * recording fill the ALUs.  The level also decides whose hardware queue the stream shares: the runtime pools its queues per priority,
+ * so a stream at a level nothing else in the process uses has a queue to itself ("Hardware queues"). */
+int pm_ctx_create_prio(int device, int level, pm_ctx **out);
+int pm_ctx_stream_priority(pm_ctx *ctx, int *h_priority);      /* hipStreamGetPriority of the context's stream (numerically lower = higher) */
 /* A context whose stream may only use the compute units whose bit is set in cu_mask (nwords x 32 bits; bit i goes to XCD
  * i mod 8, so a run of 8 k consecutive bits takes k CUs from every XCD).  The pipelined executor keeps the slicers' few, long-lived,
  * latency-bound waves on a handful of CUs of their own and the FIR kernels on the rest: a FIR workgroup that shares a SIMD with a
@@ -861,8 +865,9 @@ typedef struct pm_pipe_desc {
     int32_t slice_workers;           /* 0 = 2 */
     int32_t slice_group;             /* most recordings per slicer batch (0 = 4) */
     int32_t slice_min_group;         /* a batch waits for this many recordings while later ones are queued (0 = slice_group) */
-    int32_t demod_streams;           /* recordings take turns on this many demod streams: the context's own and further ones of the
-                                        pipeline's, each with its own band-passed stream and sweep state (0 = 2) */
+    int32_t demod_streams;           /* recordings take turns on this many demod streams of the pipeline's own (each starts a recording
+                                        behind the point the caller's stream had reached at its submission), each with its own
+                                        band-passed stream and sweep state (0 = 2) */
     int32_t host_threads;            /* recordings in the host stage at once (0 = min(12, 36 / chains), at least 2) */
     int32_t decode_threads;          /* threads inside one recording's host stage (0 = one per chain) */
     double address_distance;         /* PacketMetaArray.Correlate (packet_meta.py:230); < 0: no de-dup here (the chains are a part of
@@ -911,7 +916,7 @@ int pm_pipe_release(pm_pipe *pipe, int64_t ticket);      /* the result's memory 
 int pm_pipe_drain(pm_pipe *pipe);                        /* every recording submitted so far is through */
 int pm_pipe_stats(pm_pipe *pipe, int64_t *h_batches, int64_t *h_batch_recordings, double *h_slice_busy_ms, double *h_host_busy_ms);
 pm_ctx *pm_pipe_side_ctx(pm_pipe *pipe, int worker);     /* a slicer worker's context (NULL past the last): for pm_prof_* */
-pm_ctx *pm_pipe_demod_ctx(pm_pipe *pipe, int k);         /* demod stream k (0 = the caller's context; NULL past the last) */
+pm_ctx *pm_pipe_demod_ctx(pm_pipe *pipe, int k);         /* demod stream k (NULL past the last); the pipeline's own, except stream 0 under pipe_queue_plan 0: the caller's context */
 int pm_pipe_destroy(pm_pipe *pipe);                      /* drains first */
 
 #ifdef __cplusplus

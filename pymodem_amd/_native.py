@@ -305,6 +305,7 @@ _SIGS = {
     "pm_last_error": ([ctypes.c_char_p, ctypes.c_size_t], _int),
     "pm_ctx_create": ([_int, ctypes.POINTER(_vp)], _int),
     "pm_ctx_create_prio": ([_int, _int, ctypes.POINTER(_vp)], _int),
+    "pm_ctx_stream_priority": ([_vp, ctypes.POINTER(_int)], _int),
     "pm_ctx_tune": ([_vp, ctypes.c_char_p, _i64], _int),
     "pm_ctx_tuned": ([_vp, ctypes.c_char_p, ctypes.POINTER(_i64)], _int),
     "pm_d2d": ([_vp, _vp, _vp, ctypes.c_size_t], _int),

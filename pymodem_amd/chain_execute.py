@@ -1217,16 +1217,18 @@ class NativePipeline:
         return {"slice_batches": b.value, "recordings": r.value, "slice_busy_ms": s.value, "host_busy_ms": h.value}
 
     def side_contexts(self):
-        """The contexts the library owns -- the slicer workers' and the demod streams beyond the caller's: for Context.profile /
-        profile_read / sync."""
-        out = []
-        for entry, first in ((lib().pm_pipe_side_ctx, 0), (lib().pm_pipe_demod_ctx, 1)):
-            i = first
+        """The contexts the library owns -- the slicer workers' and the pipeline's own demod streams, each once and never the caller's
+        (demod stream 0 under pipe_queue_plan 0): for Context.profile / profile_read / sync."""
+        out, seen = [], {self._ctx.handle.value}
+        for entry in (lib().pm_pipe_side_ctx, lib().pm_pipe_demod_ctx):
+            i = 0
             while True:
                 c = entry(self._h, i)
                 if not c:
                     break
-                out.append(Context.borrowed(c, self._ctx.device))
+                if c not in seen:
+                    seen.add(c)
+                    out.append(Context.borrowed(c, self._ctx.device))
                 i += 1
         return out
 

@@ -89,12 +89,13 @@ struct RowBlock {
 }  // namespace
 
 struct pm_pipe {
-    pm_ctx *ctx = nullptr;               // the caller's context: the first demod stream
-    std::vector<pm_ctx *> demod;         // demod streams, recordings take turns (demod[0] == ctx, the others are the pipeline's)
+    pm_ctx *ctx = nullptr;               // the caller's context: recordings are handed over from its stream, buffers come from it
+    std::vector<pm_ctx *> demod;         // demod streams, recordings take turns; the pipeline's own from demod_own on
+    size_t demod_own = 0;                // (queue plan 0: 1, demod[0] == ctx)
     std::vector<double *> d_bpf_outs;    // one band-passed stream per demod context
     pm_bpf8_plan *bpf8 = nullptr;        // the band-pass on the int8 matrix pipe (every sweep certified, <= 177 taps; PM_PIPE_BPF8=0: off)
     std::vector<pm_lpf8_plan *> lpf8;    // per sweep: its low-pass there too (tones, <= 113 taps; PM_PIPE_LPF8=0: off), else nullptr
-    std::vector<hipEvent_t> handover;    // per slot: the point of the caller's stream a recording submitted to another demod stream starts behind
+    std::vector<hipEvent_t> handover;    // per slot: the point of the caller's stream a recording on a demod stream of the pipeline's starts behind
     std::vector<pm_ctx *> side;          // slicer streams, one per worker
     int nchains = 0, nsweeps = 0, slots = 16, group = 4, min_group = 4, host_threads = 3, decode_threads = 8;
     double address_distance = 0, x_bound = 0;
@@ -253,6 +254,24 @@ Rec::~Rec()
 {
     if (rowblock && owner) rows_retire(owner, rowblock);
     else delete rowblock;
+}
+
+// Where the pipeline's streams are made.  The runtime keeps a pool of hardware queues per priority level, GPU_MAX_HW_QUEUES of each, and a
+// new stream joins the least used queue of its level's pool -- whatever else the process has made there first: torch's streams, a
+// communicator's, the caller's.  Two streams on one queue take turns, and the demod streams' launches must not (two recordings' fused
+// launches side by side are what the two streams are for), nor the slicers'.  So a level per role (pm_ctx_create_prio):
+//   plan 1 (default)  every demod stream the pipeline's own at the LOWEST level, a pool nothing else in the process uses; slicers highest
+//   plan 0            the streams from before the plan: demod[0] the caller's, the other demod streams plain, slicers highest
+// In every plan the slicers stay strictly above the demod streams: the walkers' small launches must get freed slots first.
+struct QueuePlan {
+    int demod_level, slicer_level;
+    bool caller_demod;                   // demod[0] is the caller's stream, not one of the pipeline's
+};
+
+QueuePlan pipe_queue_plan(const pm_tuning &t)
+{
+    if (t.pipe_queue_plan == 0) return QueuePlan{0, 1, true};
+    return QueuePlan{-1, 1, false};
 }
 
 int fail(Rec &r, int rc)
@@ -710,14 +729,14 @@ int pm_pipe_destroy(pm_pipe *p)
     for (auto &t : p->threads) t.join();
     pm_ctx *ctx = p->ctx;
     (void)pm_ctx_sync(ctx);
+    for (size_t i = p->demod_own; i < p->demod.size(); ++i) (void)pm_ctx_sync(p->demod[i]);     // (the bitmaps' and band-passed streams' writers)
     for (uint64_t *b : p->d_bits)
         if (b) (void)pm_free(ctx, b);
-    for (size_t i = 1; i < p->demod.size(); ++i) (void)pm_ctx_sync(p->demod[i]);
     for (double *b : p->d_bpf_outs)
         if (b) (void)pm_free(ctx, b);
     pm_bpf8_plan_destroy(p->bpf8);
     for (pm_lpf8_plan *q : p->lpf8) pm_lpf8_plan_destroy(q);
-    for (size_t i = 1; i < p->demod.size(); ++i) (void)pm_ctx_destroy(p->demod[i]);
+    for (size_t i = p->demod_own; i < p->demod.size(); ++i) (void)pm_ctx_destroy(p->demod[i]);
     for (hipEvent_t e : p->handover)
         if (e) (void)hipEventDestroy(e);
     if (p->d_cells) (void)hipFree(p->d_cells);
@@ -757,6 +776,7 @@ int pm_pipe_create(pm_ctx *ctx, const pm_pipe_desc *desc, pm_pipe **out)
     // two: with the sweeps' sums on the matrix pipe three recordings' demod kernels at once take longer than three in a row
     // (demod alone 0.67 ms per recording with three streams, 0.49 with two, 0.84 with one)
     const int nd = d.demod_streams > 0 ? std::min(d.demod_streams, 4) : 2;
+    const QueuePlan plan = pipe_queue_plan(ctx->tune);
     p->slots = std::max(2, p->slots);
     p->keep_slices = d.keep_slices != 0;
     p->frames = ctx->tune.pipe_frames != 0;
@@ -840,10 +860,16 @@ int pm_pipe_create(pm_ctx *ctx, const pm_pipe_desc *desc, pm_pipe **out)
         if (rc) break;
         const int64_t nb = d.nsweeps ? d.max_samples - d.mb + 1 : 1;
         void *q = nullptr;
-        p->demod.push_back(ctx);
-        for (int k = 1; k < nd && !rc; ++k) {
+        if (plan.caller_demod) {
+            p->demod.push_back(ctx);
+            p->demod_own = 1;
+        }
+        for (int k = (int)p->demod.size(); k < nd && !rc; ++k) {
             pm_ctx *c = nullptr;
-            if (!(rc = pm_ctx_create_prio(ctx->device, 0, &c))) p->demod.push_back(c);
+            if (!(rc = pm_ctx_create_prio(ctx->device, plan.demod_level, &c))) {
+                p->demod.push_back(c);
+                if (!plan.caller_demod) c->tune = ctx->tune;     // the caller's switches, as its own stream had them when it was demod[0]
+            }
         }
         for (int k = 0; k < nd && !rc; ++k)
             if (!(rc = pm_malloc(ctx, (size_t)nb * sizeof(double), &q))) p->d_bpf_outs.push_back((double *)q);
@@ -917,7 +943,7 @@ int pm_pipe_create(pm_ctx *ctx, const pm_pipe_desc *desc, pm_pipe **out)
             // (confining the slicer streams to 4 / 8 / 12 / 16 CUs per XCD was measured: 1.64 / 1.13 / 0.98 / 0.89 ms per step against
             // 0.81 -- the walkers need the width; at 8 per XCD they alone take 1.1 ms per recording, i.e. the slicers are worth a
             // third of the whole GPU's time per recording)
-            if (!(rc = pm_ctx_create_prio(ctx->device, 1, &s))) {
+            if (!(rc = pm_ctx_create_prio(ctx->device, plan.slicer_level, &s))) {
                 p->side.push_back(s);
                 s->tune.bitscan_tile_words = ctx->tune.bitscan_tile_words;
                 s->tune.bitscan_frame_words = ctx->tune.bitscan_frame_words;
@@ -988,8 +1014,8 @@ int pm_pipe_submit(pm_pipe *p, const int16_t *d_audio, int64_t n, int64_t *h_tic
     r->dctx = p->demod[di];
     int rc = PM_OK;
     if (r->dctx != p->ctx) {
-        // the recording is in place at this point of the CALLER's stream (an upload enqueued there, an event it waits for): the other
-        // demod stream starts behind that point
+        // the recording is in place at this point of the CALLER's stream (an upload enqueued there, an event it waits for): a demod
+        // stream of the pipeline's own starts behind that point
         if (hipEventRecord(p->handover[r->slot], p->ctx->stream) != hipSuccess || hipStreamWaitEvent(r->dctx->stream, p->handover[r->slot], 0) != hipSuccess)
             rc = pm_set_error(PM_ERR_HIP, "handing the recording to demod stream %zu failed", di);
     }

@@ -35,7 +35,7 @@ const TuneKey kTuneKeys[] = {
     {"bitscan_tile_words", "PM_BITSCAN_TILE_WORDS", &pm_tuning::bitscan_tile_words}, {"pipe_scan", "PM_PIPE_SCAN", &pm_tuning::pipe_scan},
     {"bitscan_frame_words", "PM_BITSCAN_FRAME_WORDS", &pm_tuning::bitscan_frame_words}, {"pipe_frames", "PM_PIPE_FRAMES", &pm_tuning::pipe_frames},
     {"bitscan_packet_waves", "PM_BITSCAN_PACKET_WAVES", &pm_tuning::bitscan_packet_waves}, {"pipe_packets", "PM_PIPE_PACKETS", &pm_tuning::pipe_packets},
-    {"pipe_addrs", "PM_PIPE_ADDRS", &pm_tuning::pipe_addrs},
+    {"pipe_addrs", "PM_PIPE_ADDRS", &pm_tuning::pipe_addrs}, {"pipe_queue_plan", "PM_PIPE_QUEUE_PLAN", &pm_tuning::pipe_queue_plan},
     {"sweep_no_tail", "PM_SWEEP_NO_TAIL", &pm_tuning::sweep_no_tail}, {"afsk_split", "PM_AFSK_SPLIT", &pm_tuning::afsk_split}, {"fused_lds_pad", "PM_FUSED_LDS_PAD", &pm_tuning::fused_lds_pad}, {"sweep_lds_templates", "PM_SWEEP_LDS_TEMPLATES", &pm_tuning::sweep_lds_templates},
 };
 }  // namespace
@@ -89,27 +89,42 @@ int pm_last_error(char *buf, size_t cap)
 
 int pm_ctx_create(int device, pm_ctx **out) { return pm_ctx_create_prio(device, 0, out); }
 
-int pm_ctx_create_prio(int device, int high_priority, pm_ctx **out)
+// level: 1 the device's highest stream priority, 0 a plain stream, -1 its lowest.  The runtime keeps a pool of hardware queues per priority
+// (GPU_MAX_HW_QUEUES of each) and a new stream joins the least used queue of its pool: the level also says whose queues it shares.
+int pm_ctx_create_prio(int device, int level, pm_ctx **out)
 {
     PM_ARG(out != nullptr);
+    PM_ARG(level >= -1 && level <= 1);
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0)
         return pm_set_error(PM_ERR_NODEV, "no HIP device visible: the HIP path cannot run (there is no CPU fallback)");
     PM_ARG(device >= 0 && device < n);
     PM_HIP(hipSetDevice(device));
+    int lo = 0, hi = 0;                                       // numerically lower = higher priority
+    if (level) PM_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
     pm_ctx *c = new pm_ctx();
     c->device = device;
-    if (high_priority) {
-        int lo = 0, hi = 0;                                   // numerically lower = higher priority
-        PM_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        PM_HIP(hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, hi));
-    } else {
-        PM_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    hipError_t e;
+    if (level && lo != hi)                                    // (one level only: a plain stream whatever was asked for)
+        e = hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, level > 0 ? hi : lo);
+    else
+        e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
+    if (e != hipSuccess) {
+        delete c;
+        return pm_set_error(PM_ERR_HIP, "creating a stream of priority level %d failed: %s", level, hipGetErrorString(e));
     }
     PM_HIP(hipEventCreate(&c->ev0));
     PM_HIP(hipEventCreate(&c->ev1));
     PM_HIP(hipHostMalloc(&c->h_pinned, PM_PINNED_BYTES, hipHostMallocDefault));
     *out = c;
+    return PM_OK;
+}
+
+int pm_ctx_stream_priority(pm_ctx *c, int *h_priority)
+{
+    PM_CTX(c);
+    PM_ARG(h_priority != nullptr);
+    PM_HIP(hipStreamGetPriority(c->stream, h_priority));
     return PM_OK;
 }
 
