@@ -6,9 +6,7 @@
 #include "pm_fir_dev.h"
 #include "pm_bpf8_dev.h"
 #include "pm_afsk_sweep.h"
-#include <chrono>
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 
 namespace {
@@ -586,17 +584,7 @@ __global__ __launch_bounds__(kThreads) void fir_sweep_kernel(const double *__res
 // x (the first ceil((2047 + ml) / L) lanes do, e.g. 179 of 256 for ml = 100: three waves with short runs beat two with long ones), lays them out as the FIR's padded LDS images -- the
 // space image over the window of x, which is dead by then -- and every thread takes its 8 outputs of each low-pass from there.
 // ONE: a single chain, its mark - gain * space difference as the only image.  Arithmetic and bound: afsk_slide_kernel + fir_valid_kernel
-// + fir_sweep_kernel, value for value.
-inline size_t fuse_region0(int m, int ml, int L = kFuseRun)
-{
-    const int nmag = kThreads * 8 + ml - 1, nruns = (nmag + L - 1) / L;
-    const int p = nruns * L + m - 1;
-    const int a = p + p / L + 2, b = slot<8>(nmag) + 2;
-    return (size_t)((a > b ? a : b) + 1) / 2 * 2;
-}
-inline size_t fuse_image(int ml) { return (size_t)(slot<8>(kThreads * 8 + ml - 1) + 3) / 2 * 2; }
-inline size_t fuse_lds_bytes(int m, int ml, int L = kFuseRun) { return (fuse_region0(m, ml, L) + fuse_image(ml) + 4 * (size_t)m) * sizeof(double); }
-
+// + fir_sweep_kernel, value for value.  LDS: fuse_region0 / fuse_image / fuse_lds_bytes (pm_afsk_sweep.h).
 template <bool ONE, int L = kFuseRun>
 __global__ __launch_bounds__(kThreads) void afsk_slide_lpf_kernel(const double *__restrict__ x, int64_t n, const double *__restrict__ mi,
                                                                   const double *__restrict__ mq, const double *__restrict__ ui,
@@ -684,7 +672,7 @@ struct SweepTail {
 };
 
 // The exact chain of ONE (sample, modem) pair by a whole workgroup, every sum in the canonical order of fir_valid_kernel /
-// afsk_correlate_kernel (= sweep_exact_kernel below, value for value): the mc + ml - 1 band-pass outputs under the entry (one thread
+// afsk_correlate_kernel (sweep_exact_kernel below runs it per list entry, a wave each): the mc + ml - 1 band-pass outputs under the entry (one thread
 // each, from the audio; or read from x), the ml correlator-bank outputs (one thread each, four sums side by side), the low-pass sum
 // (thread 0).  `dd`: (2 ml + 2 mc + 2 mb - 2 + 4 mc + ...) doubles of LDS nobody else uses any more.  Ends with a barrier.
 template <int THREADS>
@@ -1177,7 +1165,8 @@ __global__ void sweep_mail_reset_kernel(int *__restrict__ count, int *__restrict
 // The exact chain for single samples: correlator bank of modem g at the ml positions the low-pass needs, then the low-pass, every
 // sum in the canonical order of afsk_correlate_kernel / fir_valid_kernel.  Runs after fir_sweep_kernel (its bitmap bytes are final).
 // AUDIO: the band-passed stream the sweep saw was itself a value with a bound (pm_bpf8.hip), so the recomputation starts one stage
-// earlier -- the mc + ml - 1 band-pass outputs under the entry from the int16 audio, the reference's sum in fir_valid_kernel's order.
+// earlier -- the mc + ml - 1 band-pass outputs under the entry from the int16 audio, the reference's sum in fir_valid_kernel's order:
+// sweep_tail_entry with the wave as its workgroup (LDS: sweep_tail_doubles).
 template <bool AUDIO>
 __global__ __launch_bounds__(64) void sweep_exact_kernel(const double *__restrict__ x, const double *__restrict__ mi, const double *__restrict__ mq,
                                                          const double *__restrict__ space, int mc, const double *__restrict__ lpf, int ml,
@@ -1211,47 +1200,7 @@ __global__ __launch_bounds__(64) void sweep_exact_kernel(const double *__restric
         if (g >= kSweepMax || P.bits[g] == nullptr) continue;                    // not an entry of this sweep (cannot happen: see sweep_signs)
         const double *si = space + (size_t)g * 2 * mc, *sq = si + mc;
         if (AUDIO) {
-            // The audio under the entry and every tap set once, coalesced, into LDS; then the sums from there.  (From global memory --
-            // a tap load in front of every fma of three chained sums -- this kernel took 160-200 us for twenty entries, on the demod
-            // stream, twice per recording.)
-            const int nw = ml + mc - 1, na = nw + src.mb - 1;
-            double *xw = dd + ml, *aw = xw + nw, *tb = aw + na, *tc = tb + src.mb, *tl = tc + 4 * mc;
-            for (int p = lane; p < na; p += 64) aw[p] = (double)src.audio[k + p];
-            for (int t = lane; t < src.mb; t += 64) tb[t] = src.bpf[src.mb - 1 - t];
-            for (int t = lane; t < mc; t += 64) {
-                tc[4 * t + 0] = mi[mc - 1 - t];
-                tc[4 * t + 1] = mq[mc - 1 - t];
-                tc[4 * t + 2] = si[mc - 1 - t];
-                tc[4 * t + 3] = sq[mc - 1 - t];
-            }
-            for (int t = lane; t < ml; t += 64) tl[t] = lpf[ml - 1 - t];
-            __syncthreads();
-            for (int p = lane; p < nw; p += 64) {
-                double acc = 0.0;
-                for (int t = 0; t < src.mb; ++t) acc = __builtin_fma(tb[t], aw[p + t], acc);
-                xw[p] = acc;
-            }
-            __syncthreads();
-            for (int j = lane; j < ml; j += 64) {
-                double a = 0.0, b = 0.0, c = 0.0, d = 0.0;
-                for (int t = 0; t < mc; ++t) {
-                    const double v = xw[j + t];
-                    a = __builtin_fma(tc[4 * t + 0], v, a);
-                    b = __builtin_fma(tc[4 * t + 1], v, b);
-                    c = __builtin_fma(tc[4 * t + 2], v, c);
-                    d = __builtin_fma(tc[4 * t + 3], v, d);
-                }
-                dd[j] = __builtin_sqrt(a * a + b * b) - __builtin_sqrt(c * c + d * d);
-            }
-            __syncthreads();
-            if (lane == 0) {
-                double acc = 0.0;
-                for (int j = 0; j < ml; ++j) acc = __builtin_fma(tl[j], dd[j], acc);
-                unsigned long long *w = reinterpret_cast<unsigned long long *>(P.bits[g]) + (k >> 6);
-                const unsigned long long bit = 1ull << (k & 63);
-                if (acc >= 0.0) atomicOr(w, bit); else atomicAnd(w, ~bit);
-            }
-            __syncthreads();
+            sweep_tail_entry<64>(dd, lane, x, mi, mq, si, sq, mc, lpf, ml, src, k, reinterpret_cast<unsigned long long *>(P.bits[g]));
             continue;
         }
         for (int j = lane; j < ml; j += 64) {
@@ -1455,202 +1404,91 @@ static int afsk_magnitudes(pm_ctx *ctx, const double *d_x, int64_t n, double x_b
     return PM_OK;
 }
 
-// one wave per uncertain decision at a time: as many workgroups as a sweep usually has entries (several hundred; an idle one costs a
-// dispatch slot for a microsecond), so that the launch lasts one entry's latency and not three
-constexpr int kExactGrid = 4096;
+}  // extern "C"
 
-static int sweep_signs(pm_ctx *ctx, const double *d_x, int64_t n, double x_bound, const double *d_mark_i, const double *d_mark_q,
-                       const double *d_unit_i, const double *d_unit_q, const double *d_space, const double *h_gains, int groups, int m,
-                       const double *d_lpf, int ml, double lpf_abs_sum, uint64_t *const *h_bits, const pm_afsk_tones *tones,
-                       const SweepSource *src = nullptr, const pm_lpf8_plan *lpf8 = nullptr, int *own_count = nullptr, int *own_mail = nullptr,
-                       unsigned long long *own_list = nullptr)
-{
-    PM_CTX(ctx);
-    // own_list (with own_count): the recording's own list of kSweepCap entries -- a sweep on the matrix pipe then decides its uncertain
-    // samples inside its workgroups, counts what did not fit (normally nothing) in own_count, NO launch follows it and own_mail is not
-    // written: the caller mails the counters of all the recording's sweeps at once (sweep_mail_kernel) and whoever reads the mail runs
-    // pm_afsk_sweep_exact_list over a list that is not empty
-    PM_ARG(!own_list || own_count);
-    // own_count / own_mail: the caller's counter and mailbox word for this sweep (pm_sweep_cells: zeroed by an earlier launch on this
-    // stream, read by the caller when the stream has passed this sweep); the context's ring stays where it is
-    PM_ARG((own_count == nullptr) == (own_mail == nullptr) && (!own_count || ctx->sweep_deferred));
-    PM_ARG(d_x && d_mark_i && d_mark_q && d_unit_i && d_unit_q && d_space && h_gains && d_lpf && h_bits);
-    // a band-passed stream that is only near the reference's: certified decisions with the deferred fallback only (the gated exact
-    // launches below read d_x), and the exact recomputation goes back to the audio
-    PM_ARG(!src || (src->audio && src->bpf && src->mb >= 1 && src->e_x >= 0.0 && src->e_x < 1e-6 * x_bound && ctx->sweep_deferred && tones));
-    // everything that can refuse the call is checked before the counter ring moves on: a sweep that takes its slot and then launches
-    // nothing leaves the NEXT sweep's slot uncleared (each sweep's last launch clears it), and that sweep would start from whatever
-    // count the slot held 64 sweeps ago -- up to 65536 stale list entries to "recompute"
-    PM_ARG(!tones || (tones->tap_dev >= 0.0 && tones->tap_dev < 1e-6));
-    PM_ARG(groups >= 1 && groups <= kSweepMax && m >= 1 && m <= kMaxTaps && ml >= 1 && ml <= kMaxTaps);
-    PM_ARG(x_bound > 0.0 && x_bound < 1e300 && lpf_abs_sum > 0.0 && lpf_abs_sum < 1e300);
-    PM_ARG(n >= (int64_t)m + ml - 1);
-    const int64_t nc = n - m + 1, nl = nc - ml + 1;
+// ---- one certified sweep as every launcher sees it ---------------------------------------------------------------------------------------
+// Made by sweep_plan() from the caller's description, which performs EVERY check that can refuse a sweep: a refused sweep has touched
+// neither the stream nor a counter.
+struct SweepPlan {
+    pm_afsk_sweep_desc w;
+    int64_t nc, nl;                  // magnitudes per stream; low-pass outputs = bits per modem
     SweepArgs P;
-    double gmax = 0.0;
-    PM_ARG(sweep_args(h_gains, h_bits, groups, &P, &gmax));
-    const int cap = kSweepCap;                             // more uncertain samples than this: the gated exact path below takes over
-    const int F = 2 + 2 * groups;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const int64_t stride = (nc + 63) / 64 * 64;
-    const size_t b_m = up((size_t)nc * 8), b_a = up((size_t)nl * 8), b_list = up((size_t)cap * 8), b_w = up((size_t)F * m * 8),
-                 b_c = up((size_t)stride * groups * 8);
-    if (int rc = pm_scratch_reserve(ctx, 2 * b_m + b_a + b_list + 256 + b_w + b_c)) return rc;
-    char *base = (char *)ctx->d_scratch;
-    double *M = (double *)base, *S = (double *)(base + b_m), *A = (double *)(base + 2 * b_m);
-    unsigned long long *list = own_list ? own_list : (unsigned long long *)(base + 2 * b_m + b_a);
-    // The counter of uncertain samples lives in a small ring of its own (not in the scratch block, which the next call on this
-    // context re-carves and may re-allocate: pm_afsk_sweep_last reads it later).  All slots start at zero; the last launch of a
-    // sweep clears the slot the next sweep will use, so there is no memset on the stream.
-    if (!own_count && !ctx->d_sweep) {
+    double gmax;
+    SlideTones T;                    // with tones
+    SweepSource src;                 // audio == nullptr: the input is the reference's band-passed stream
+    SweepRouting R;
+    double E;
+    Lpf8Args Q;                      // kFused8 on the caller's plan: its constants
+};
+
+static SweepSwitches sweep_switches(const pm_tuning &t) { return SweepSwitches{t.afsk_unfused != 0, t.afsk_lpf8 == 1, t.sweep_no_tail != 0, t.afsk_split != 0}; }
+
+// n: length of the sweep's input; src: nullptr, or where a band-passed stream that is only near the reference's came from; lpf8: nullptr or
+// the caller's matrix-pipe plan of the low-pass; own_list: the counts go to a recording's own list (pm_sweep_cells::d_list)
+static int sweep_plan(const pm_tuning &tune, const pm_afsk_sweep_desc &w, int64_t n, double x_bound, const SweepSource *src, const pm_lpf8_plan *lpf8,
+                      bool own_list, SweepPlan *S)
+{
+    PM_ARG(w.d_mark_i && w.d_mark_q && w.d_unit_i && w.d_unit_q && w.d_space && w.h_gains && w.d_lpf && w.h_bits);
+    // a band-passed stream that is only near the reference's: tone templates only, and the exact recomputation goes back to the audio
+    PM_ARG(!src || (src->audio && src->bpf && src->mb >= 1 && src->e_x >= 0.0 && src->e_x < 1e-6 * x_bound && w.h_tones));
+    PM_ARG(!w.h_tones || (w.h_tones->tap_dev >= 0.0 && w.h_tones->tap_dev < 1e-6));
+    PM_ARG(w.groups >= 1 && w.groups <= kSweepMax && w.m >= 1 && w.m <= kMaxTaps && w.ml >= 1 && w.ml <= kMaxTaps);
+    PM_ARG(x_bound > 0.0 && x_bound < 1e300 && w.lpf_abs_sum > 0.0 && w.lpf_abs_sum < 1e300);
+    PM_ARG(n >= (int64_t)w.m + w.ml - 1);
+    S->w = w;
+    S->nc = n - w.m + 1;
+    S->nl = S->nc - w.ml + 1;
+    PM_ARG(pm_cdiv(S->nl, kTile) < (1LL << 31));
+    PM_ARG(sweep_args(w.h_gains, w.h_bits, w.groups, &S->P, &S->gmax));
+    S->T = w.h_tones ? slide_tones(w.h_tones) : SlideTones{};
+    S->src = src ? *src : SweepSource{nullptr, nullptr, 0, 0.0};
+    S->R = sweep_route(w.m, w.ml, w.groups, w.h_tones != nullptr, S->src.mb, lpf8 ? lpf8->ml : 0, own_list, sweep_switches(tune));
+    S->E = sweep_bound(w.m, w.lpf_abs_sum, S->gmax, x_bound, w.h_tones, S->R.route >= kFused64 ? kFuseRun : kSlideRun, S->src.e_x);
+    if (S->R.route == kFused8 && !S->R.call_plan) S->Q = lpf8_args(lpf8, S->gmax, S->R.one);
+    return PM_OK;
+}
+
+// ---- who owns a sweep's counter -------------------------------------------------------------------------------------------------------------
+struct SweepCounters {
+    int *count;                      // uncertain samples the sweep could not decide itself
+    int *next;                       // the ring's next slot, which this sweep's LAST launch clears (nullptr: a recording's own cells)
+    int *mail;                       // page-locked word the sweep's last launch leaves the count in (nullptr: none)
+    unsigned long long *list;        // the recording's own list (nullptr: one in the context's scratch block)
+};
+
+// The context's ring (not in the scratch block, which the next call on this context re-carves and may re-allocate: pm_afsk_sweep_last
+// reads the counter later).  All slots start at zero; the last launch of a sweep clears the slot the next sweep will use, so there is
+// no memset on the stream.  A sweep that takes its slot and then launches nothing would leave the NEXT sweep's slot uncleared, and
+// that sweep would start from whatever count the slot held 64 sweeps ago -- up to 65536 stale list entries to "recompute": whatever
+// can refuse a sweep is checked before this is called (sweep_plan), and RingGuard covers a launch that fails afterwards.
+static int sweep_ring_take(pm_ctx *ctx, bool deferred, SweepCounters *C)
+{
+    if (!ctx->d_sweep) {
         PM_HIP(hipMalloc((void **)&ctx->d_sweep, kSweepRing * sizeof(int)));
         PM_HIP(hipMemset(ctx->d_sweep, 0, kSweepRing * sizeof(int)));
         PM_HIP(hipHostMalloc((void **)&ctx->h_sweep, kSweepRing * sizeof(int), hipHostMallocDefault));
         memset(ctx->h_sweep, 0, kSweepRing * sizeof(int));
     }
-    int *count = own_count, *count_next = nullptr, *mail = own_mail;
-    if (!own_count) {
-        count = ctx->d_sweep + (ctx->sweep_seq % kSweepRing);
-        count_next = ctx->d_sweep + ((ctx->sweep_seq + 1) % kSweepRing);
-        mail = ctx->sweep_deferred ? ctx->h_sweep + (ctx->sweep_seq % kSweepRing) : nullptr;
-        ctx->sweep_mail[ctx->sweep_seq % kSweepRing] = mail ? ctx->sweep_seq + 1 : 0;
-        ctx->sweep_seq++;
-    }
-    // a sweep that fails from here on has not run its last launch: the next sweep's counter is cleared by hand
-    struct RingGuard {
-        hipStream_t st; int *next; bool ok;
-        ~RingGuard() { if (!ok && next) (void)hipMemsetAsync(next, 0, sizeof(int), st); }
-    } ring{ctx->stream, count_next, false};
-    double *d_w = (double *)(base + 2 * b_m + b_a + b_list + 256);
-    double *C = (double *)(base + 2 * b_m + b_a + b_list + 256 + b_w);
-    if (!own_count) ctx->sweep_count = count;
-    // One chain with tone templates: its mark - gain * space difference leaves the sliding kernel as ONE stream and takes ONE
-    // low-pass (the reference's own dataflow, afsk.py:162-166, on approximate magnitudes); a sweep takes two for all its chains.
-    const bool one = groups == 1 && tones && m >= 2;
-    const double *lp_in = one ? M : S, *lp_a = one ? nullptr : A;
-    const int frun = ctx->tune.fuse_run == 16 ? 16 : kFuseRun;      // PM_FUSE_RUN=16: round 1's run length, for comparison
-    // fused: sliding sums, low-pass(es) and combine in one kernel (afsk_slide_lpf_kernel): nothing but the bitmaps is written
-    const bool fused = tones && m >= 2 && sweep_runs(ml, frun) <= kThreads && fuse_lds_bytes(m, ml, frun) <= 120 * 1024 && !ctx->tune.afsk_unfused;
-    if (!fused) {
-        if (int rc = afsk_magnitudes(ctx, d_x, n, x_bound, d_mark_i, d_mark_q, d_unit_i, d_unit_q, m, tones, M, one ? nullptr : S, P.gain[0])) return rc;
-        if (!one)
-            if (int rc = pm_fir_valid_f64(ctx, M, nc, d_lpf, ml, A, 0)) return rc;
-    }
-    const double E = sweep_bound(m, lpf_abs_sum, gmax, x_bound, tones, fused ? frun : kSlideRun, src ? src->e_x : 0.0);
-    // Low-passes on the int8 matrix pipe (afsk_slide_lpf8_kernel): a per-call plan for tests and measurements (PM_AFSK_LPF8=1), the
-    // pipeline's own otherwise
-    pm_lpf8_plan *own8 = nullptr;
-    if (fused && !lpf8 && frun == kFuseRun && ml + 15 <= 128 && ctx->tune.afsk_lpf8 == 1) {
-        std::vector<double> hl((size_t)ml);
-        PM_HIP(hipMemcpyAsync(hl.data(), d_lpf, hl.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        PM_HIP(hipStreamSynchronize(ctx->stream));
-        if (int rc = pm_lpf8_plan_create(ctx, hl.data(), ml, &own8)) return rc;
-        lpf8 = own8;
-    }
-    struct Own8 { pm_ctx *c; pm_lpf8_plan *p; ~Own8() { if (p) { (void)hipStreamSynchronize(c->stream); pm_lpf8_plan_destroy(p); } } } own8_guard{ctx, own8};
-    if (fused) {
-        const SlideTones T = slide_tones(tones);
-        const int64_t ntiles = pm_cdiv(nl, (int64_t)kThreads * 8);
-        PM_ARG(ntiles < (1LL << 31));
-        PmProf prof(ctx, PM_K_FIR_F64);
-        prof.work((double)n * 8 + (double)groups * nl / 8,
-                  (4.0 * m / frun + 18.0) * (double)nc + (one ? 1.0 : 2.0) * 2.0 * ml * (double)nl + 2.0 * groups * (double)nl);
-        int rc;
-        const bool pipe8 = lpf8 && frun == kFuseRun && lpf8->ml == ml && ml + 15 <= 128;
-        if (pipe8) {
-            const Lpf8Args Q = lpf8_args(lpf8, gmax, one);
-            const SweepShape shape{m, ml, one};
-            const Lpf8Layout Y = lpf8_layout(&shape, 1, src ? src->mb : 0, 0);
-            const SweepTail TL{d_space, d_lpf, Y.lds_ok && !ctx->tune.sweep_no_tail, src ? *src : SweepSource{nullptr, nullptr, 0, 0.0}};
-            auto go8 = [&](auto kernel) -> int {
-                if (int rc = allow_lds(kernel, Y.lds)) return rc;
-                hipLaunchKernelGGL(kernel, dim3((unsigned)ntiles), dim3(kThreads), Y.lds, ctx->stream, d_x, n, d_mark_i, d_mark_q, d_unit_i, d_unit_q, m, T,
-                                   Q, ml, nl, groups, P, E, list, count, cap, Y.region0, TL);
-                return PM_OK;
-            };
-            rc = one ? go8(afsk_slide_lpf8_kernel<true>) : go8(afsk_slide_lpf8_kernel<false>);
-        } else {
-            const size_t lds = fuse_lds_bytes(m, ml, frun);
-            const int region0 = (int)fuse_region0(m, ml, frun), image = (int)fuse_image(ml);
-            auto go = [&](auto kernel) -> int {
-                if (int rc = allow_lds(kernel, lds)) return rc;
-                hipLaunchKernelGGL(kernel, dim3((unsigned)ntiles), dim3(kThreads), lds, ctx->stream, d_x, n, d_mark_i, d_mark_q, d_unit_i, d_unit_q, m, T,
-                                   d_lpf, ml, nl, groups, P, E, list, count, cap, region0, image);
-                return PM_OK;
-            };
-            if (frun == 16) rc = one ? go(afsk_slide_lpf_kernel<true, 16>) : go(afsk_slide_lpf_kernel<false, 16>);
-            else rc = one ? go(afsk_slide_lpf_kernel<true, 12>) : go(afsk_slide_lpf_kernel<false, 12>);
-        }
-        if (rc) return rc;
-        PM_HIP(hipGetLastError());
-        if (pipe8 && own_list) { ring.ok = true; return PM_OK; }      // nothing follows on this stream: the caller mails the count
-    } else {   // B = LPF(S) and the combine step in one pass: B never reaches memory
-        constexpr int R = 8;
-        const int64_t ntiles = pm_cdiv(nl, (int64_t)kThreads * R);
-        PM_ARG(ntiles < (1LL << 31));
-        const size_t lds = lds_bytes<R>(ml);
-        PmProf prof(ctx, PM_K_FIR_F64);
-        prof.work((double)nc * 8 + (one ? 0.0 : (double)nl * 8) + (double)groups * nl / 8, 2.0 * ml * (double)nl + 2.0 * groups * (double)nl);
-        auto go = [&](auto kernel) -> int {
-            if (int rc = allow_lds(kernel, lds)) return rc;
-            hipLaunchKernelGGL(kernel, dim3((unsigned)ntiles), dim3(kThreads), lds, ctx->stream, lp_in, nc, d_lpf, ml, lp_a, nl, groups, P, E, list, count, cap);
-            return PM_OK;
-        };
-        if (int rc = (((uintptr_t)lp_in) & 15) == 0 ? go(fir_sweep_kernel<R, true>) : go(fir_sweep_kernel<R, false>)) return rc;
-        PM_HIP(hipGetLastError());
-    }
-    {
-        PmProf prof(ctx, PM_K_SIGNS);
-        if (src)
-            hipLaunchKernelGGL(sweep_exact_kernel<true>, dim3(kExactGrid), dim3(64), (size_t)(4 * ml + 6 * m + 2 * src->mb - 3) * sizeof(double), ctx->stream, d_x, d_mark_i, d_mark_q,
-                               d_space, m, d_lpf, ml, P, list, count, cap, count_next, mail, *src);
-        else
-            hipLaunchKernelGGL(sweep_exact_kernel<false>, dim3(kExactGrid), dim3(64), (size_t)ml * sizeof(double), ctx->stream, d_x, d_mark_i, d_mark_q, d_space, m,
-                               d_lpf, ml, P, list, count, cap, ctx->sweep_deferred ? count_next : nullptr, mail, SweepSource{nullptr, nullptr, 0, 0.0});
-    }
-    PM_HIP(hipGetLastError());
-    // Deferred fallback: the caller looks at the counter once the sweep has finished (pm_afsk_sweep_result) and runs the exact
-    // chains itself in the (degenerate) overflow case; the three gated launches below -- which in the normal case only look at
-    // the counter and leave, but cost the demod stream three dispatches per sweep -- are not enqueued.
-    if (ctx->sweep_deferred) { ring.ok = true; return PM_OK; }
-    // More uncertain samples than the list holds (degenerate input: silence, amplitudes far below the caller's bound): the exact
-    // chain of every modem runs after all -- the same launches as pm_afsk_correlate_group + pm_fir_signs_f64_batch, each workgroup
-    // of which first looks at the counter and leaves at once in the normal case.  No host round trip either way.
-    hipLaunchKernelGGL(pack_group_taps_kernel, dim3((unsigned)pm_cdiv((int64_t)F * m, 256)), dim3(256), 0, ctx->stream, d_mark_i, d_mark_q,
-                       d_space, m, F, d_w);
-    if (int rc = afsk_group_dispatch(ctx, groups, d_x, n, d_w, m, C, stride, nc, count, cap)) return rc;
-    const double *cx[kSweepMax];
-    int64_t cn[kSweepMax];
-    for (int g = 0; g < groups; ++g) { cx[g] = C + (size_t)g * stride; cn[g] = nc; }
-    if (int rc = pm_fir_signs_batch(ctx, groups, cx, cn, d_lpf, ml, h_bits, 0, count, cap, count_next)) return rc;
-    ring.ok = true;
+    const int slot = (int)(ctx->sweep_seq % kSweepRing);
+    *C = SweepCounters{ctx->d_sweep + slot, ctx->d_sweep + (slot + 1) % kSweepRing, deferred ? ctx->h_sweep + slot : nullptr, nullptr};
+    ctx->sweep_mail[slot] = deferred ? ctx->sweep_seq + 1 : 0;
+    ctx->sweep_seq++;
+    ctx->sweep_count = C->count;
     return PM_OK;
 }
 
-int pm_afsk_sweep_signs(pm_ctx *ctx, const double *d_x, int64_t n, double x_bound, const double *d_mark_i, const double *d_mark_q,
-                        const double *d_unit_i, const double *d_unit_q, const double *d_space, const double *h_gains, int groups, int m,
-                        const double *d_lpf, int ml, double lpf_abs_sum, uint64_t *const *h_bits)
-{
-    return sweep_signs(ctx, d_x, n, x_bound, d_mark_i, d_mark_q, d_unit_i, d_unit_q, d_space, h_gains, groups, m, d_lpf, ml, lpf_abs_sum, h_bits, nullptr);
-}
+// a sweep that fails behind sweep_ring_take has not run its last launch: the next sweep's counter is cleared by hand
+struct RingGuard {
+    hipStream_t st; int *next; bool ok;
+    ~RingGuard() { if (!ok && next) (void)hipMemsetAsync(next, 0, sizeof(int), st); }
+};
 
-int pm_afsk_sweep_signs_tones(pm_ctx *ctx, const double *d_x, int64_t n, double x_bound, const double *d_mark_i, const double *d_mark_q,
-                              const double *d_unit_i, const double *d_unit_q, const double *d_space, const double *h_gains, int groups, int m,
-                              const double *d_lpf, int ml, double lpf_abs_sum, uint64_t *const *h_bits, const pm_afsk_tones *h_tones)
-{
-    if (!h_tones) return pm_set_error(PM_ERR_ARG, "pm_afsk_sweep_signs_tones: no tones");
-    return sweep_signs(ctx, d_x, n, x_bound, d_mark_i, d_mark_q, d_unit_i, d_unit_q, d_space, h_gains, groups, m, d_lpf, ml, lpf_abs_sum, h_bits, h_tones);
-}
+extern "C" {
 
-int pm_afsk_magnitudes(pm_ctx *ctx, const double *d_x, int64_t n, double x_bound, const double *d_mark_i, const double *d_mark_q,
-                       const double *d_space_i, const double *d_space_q, int m, const pm_afsk_tones *h_tones, double *d_mark_mag,
-                       double *d_space_mag, double *h_bound)
+int pm_afsk_sweep_mode(pm_ctx *ctx, int deferred)
 {
-    PM_CTX(ctx);
-    PM_ARG(d_x && d_mark_i && d_mark_q && d_space_i && d_space_q && d_mark_mag && d_space_mag);
-    PM_ARG(m >= 1 && m <= kMaxTaps && n >= m && x_bound > 0.0 && x_bound < 1e300);
-    if (int rc = afsk_magnitudes(ctx, d_x, n, x_bound, d_mark_i, d_mark_q, d_space_i, d_space_q, m, h_tones, d_mark_mag, d_space_mag)) return rc;
-    if (h_bound) *h_bound = h_tones && m >= 2 ? slide_bound(h_tones, m, x_bound) : 0.0;
+    PM_ARG(ctx != nullptr);
+    ctx->sweep_deferred = deferred != 0;
     return PM_OK;
 }
 
@@ -1664,208 +1502,6 @@ int pm_afsk_sweep_last(pm_ctx *ctx, int64_t *h_uncertain)
     PM_HIP(hipMemcpyAsync(&v, ctx->sweep_count, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     PM_HIP(hipStreamSynchronize(ctx->stream));
     *h_uncertain = v;
-    return PM_OK;
-}
-
-int pm_afsk_group_run(pm_ctx *ctx, const int16_t *d_audio, int64_t n, const double *d_bpf, int mb, double *d_bpf_out, double x_bound,
-                      const pm_afsk_sweep_desc *h_sweeps, int nsweeps, int64_t *h_tickets)
-{
-    return pm_afsk_group_run_plan(ctx, d_audio, n, d_bpf, mb, d_bpf_out, x_bound, h_sweeps, nsweeps, h_tickets, nullptr, nullptr);
-}
-
-}  // extern "C"
-
-// The fused launch of pm_afsk_group_run_plan (afsk_fused8_kernel): what each sweep's certified decision needs comes from where
-// sweep_signs takes it (pm_afsk_sweep.h), sweep by sweep.  -> PM_OK and *fused = true when the launch was made; *fused = false (and nothing enqueued) when
-// the group does not qualify and the caller takes the split path.
-static int afsk_group_run_fused(pm_ctx *ctx, const int16_t *d_audio, int64_t n, const double *d_bpf, int mb, double x_bound, const pm_afsk_sweep_desc *h_sweeps,
-                                int nsweeps, const pm_bpf8_plan *plan, const pm_lpf8_plan *const *lpf8, const pm_sweep_cells *cells, bool *fused)
-{
-    *fused = false;
-    if (!plan || !lpf8 || !cells || !cells->d_list || nsweeps < 1 || nsweeps > 2 || ctx->tune.afsk_split || ctx->tune.afsk_unfused || ctx->tune.fuse_run == 16 ||
-        ((uintptr_t)d_audio & 15) != 0)
-        return PM_OK;
-    int kb = 0;
-    const void *btab = nullptr;
-    double sc6[6];
-    if (pm_bpf8_plan_view(plan, &kb, &btab, sc6) != PM_OK || (kb != 3 && kb != 4)) return PM_OK;
-    FusedArgs A;
-    memset(&A, 0, sizeof(A));
-    const int64_t nb = n - mb + 1;
-    const double e_x = pm_bpf8_error(plan);
-    if (!(e_x >= 0.0 && e_x < 1e-6 * x_bound)) return PM_OK;
-    SweepShape shape[2];
-    for (int k = 0; k < nsweeps; ++k) shape[k] = SweepShape{h_sweeps[k].m, h_sweeps[k].ml, h_sweeps[k].groups == 1};
-    const Lpf8Layout Y = lpf8_layout(shape, nsweeps, mb, kb);
-    if (!Y.fuses) return PM_OK;                                     // a low-pass or a run count the kernel is not written for, or more than 64 KiB of LDS
-    for (int k = 0; k < nsweeps; ++k) {
-        const pm_afsk_sweep_desc &w = h_sweeps[k];
-        const pm_lpf8_plan *q = lpf8[k];
-        if (!q || !w.h_tones || w.m < 2 || q->ml != w.ml || w.groups < 1 || w.groups > kSweepMax || !w.h_bits || !w.h_gains) return PM_OK;
-        if (!(w.h_tones->tap_dev >= 0.0 && w.h_tones->tap_dev < 1e-6) || !(w.lpf_abs_sum > 0.0 && w.lpf_abs_sum < 1e300)) return PM_OK;
-        if (nb < (int64_t)w.m + w.ml - 1) return PM_OK;
-        FusedSweep &S = A.s[k];
-        S.mi = w.d_mark_i; S.mq = w.d_mark_q; S.ui = w.d_unit_i; S.uq = w.d_unit_q;
-        S.space = w.d_space; S.lpf = w.d_lpf;
-        {
-            // the four templates as ONE reversed, interleaved table (pack_group_taps_kernel's layout with F = 4), made the first time the
-            // plan meets these templates and kept with it: the kernel reads it through the scalar cache
-            pm_lpf8_plan *mq_ = const_cast<pm_lpf8_plan *>(q);
-            if (!(mq_->d_tpl && mq_->tpl_m == w.m && mq_->tpl_src[0] == w.d_mark_i && mq_->tpl_src[1] == w.d_mark_q && mq_->tpl_src[2] == w.d_unit_i &&
-                  mq_->tpl_src[3] == w.d_unit_q)) {
-                if (mq_->d_tpl) { PM_HIP(hipStreamSynchronize(ctx->stream)); (void)hipFree(mq_->d_tpl); mq_->d_tpl = nullptr; }
-                PM_HIP(hipMalloc(&mq_->d_tpl, sizeof(double) * 4 * (size_t)w.m + 256));
-                hipLaunchKernelGGL(pack_templates_kernel, dim3((unsigned)pm_cdiv(4 * (int64_t)w.m, 256)), dim3(256), 0, ctx->stream, w.d_mark_i, w.d_mark_q, w.d_unit_i,
-                                   w.d_unit_q, w.m, (double *)mq_->d_tpl);
-                PM_HIP(hipGetLastError());
-                PM_HIP(hipStreamSynchronize(ctx->stream));     // once per plan: another context's launch may be the table's next reader
-                mq_->tpl_m = w.m;
-                mq_->tpl_src[0] = w.d_mark_i; mq_->tpl_src[1] = w.d_mark_q; mq_->tpl_src[2] = w.d_unit_i; mq_->tpl_src[3] = w.d_unit_q;
-            }
-            S.tg = ctx->tune.sweep_lds_templates ? nullptr : (const double *)mq_->d_tpl;
-        }
-        S.m = w.m; S.ml = w.ml; S.G = w.groups;
-        S.one = w.groups == 1;
-        double gmax = 0.0;
-        if (!sweep_args(w.h_gains, w.h_bits, w.groups, &S.P, &gmax)) return PM_OK;
-        S.T = slide_tones(w.h_tones);
-        // E: the band-passed stream is a value within e_x of the reference's
-        S.E = sweep_bound(w.m, w.lpf_abs_sum, gmax, x_bound, w.h_tones, kFuseRun, e_x);
-        S.Q = lpf8_args(q, gmax, S.one);
-        S.list = cells->d_list + (size_t)k * kSweepCap;
-        S.count = cells->d_count + k;
-        S.nout = nb - w.m - w.ml + 2;
-    }
-    A.audio = d_audio;
-    A.n = n;
-    A.nb = nb;
-    A.bp_btab = (const pm_bpf8_dev::i4 *)btab;
-    for (int w = 0; w < 5; ++w) A.sc.s[w] = sc6[w];
-    A.sc.c0 = sc6[5];
-    A.src = SweepSource{d_audio, d_bpf, mb, e_x};
-    A.xs_span = Y.xs_span; A.aplane = Y.aplane; A.mmax = Y.mmax;
-    A.xw_doubles = Y.xw_doubles; A.plane_bytes = Y.plane_bytes;
-    A.cap = kSweepCap;
-    A.lds_ok = Y.lds_ok && !ctx->tune.sweep_no_tail;
-    const size_t lds_launch = Y.lds + (size_t)std::max(0, ctx->tune.fused_lds_pad);      // (PM_FUSED_LDS_PAD: fewer workgroups per CU, to measure what occupancy is worth)
-    int64_t tiles = 0;
-    double bits_out = 0.0, flops = 2.0 * mb * (double)nb;
-    for (int k = 0; k < nsweeps; ++k) {
-        tiles = std::max(tiles, pm_cdiv(A.s[k].nout, (int64_t)kThreads * 8));
-        bits_out += (double)A.s[k].G * (double)A.s[k].nout / 8;
-        flops += (4.0 * A.s[k].m / kFuseRun + 18.0) * (double)(nb - A.s[k].m + 1) + (A.s[k].one ? 1.0 : 2.0) * 2.0 * A.s[k].ml * (double)A.s[k].nout +
-                 2.0 * A.s[k].G * (double)A.s[k].nout;
-    }
-    PM_ARG(tiles >= 1 && tiles < (1LL << 31));
-    {
-        PmProf prof(ctx, PM_K_FIR_F64);
-        prof.work((double)n * 2 + bits_out, flops);          // the recording in, the bitmaps out: nothing else crosses HBM
-        auto go = [&](auto kernel) -> int {
-            if (int rc = allow_lds(kernel, lds_launch)) return rc;
-            hipLaunchKernelGGL(kernel, dim3((unsigned)tiles), dim3(kThreads), lds_launch, ctx->stream, A);
-            return PM_OK;
-        };
-        int rc = PM_OK;
-        const bool o0 = A.s[0].one != 0, o1 = nsweeps == 2 && A.s[1].one != 0;
-#define PM_FUSED_GO(KB)                                                                                                             \
-        rc = nsweeps == 1 ? (o0 ? go(afsk_fused8_kernel<KB, true, 1, false>) : go(afsk_fused8_kernel<KB, false, 1, false>))              \
-                          : (o0 ? (o1 ? go(afsk_fused8_kernel<KB, true, 2, true>) : go(afsk_fused8_kernel<KB, true, 2, false>))          \
-                                : (o1 ? go(afsk_fused8_kernel<KB, false, 2, true>) : go(afsk_fused8_kernel<KB, false, 2, false>)));
-        if (kb == 3) { PM_FUSED_GO(3) } else { PM_FUSED_GO(4) }
-#undef PM_FUSED_GO
-        if (rc) return rc;
-        PM_HIP(hipGetLastError());
-    }
-    if (int rc = sweep_mail_reset(ctx, cells, nsweeps)) return rc;
-    *fused = true;
-    return PM_OK;
-}
-
-int pm_afsk_group_run_plan(pm_ctx *ctx, const int16_t *d_audio, int64_t n, const double *d_bpf, int mb, double *d_bpf_out, double x_bound,
-                           const pm_afsk_sweep_desc *h_sweeps, int nsweeps, int64_t *h_tickets, const pm_bpf8_plan *plan,
-                           const pm_lpf8_plan *const *lpf8, const pm_sweep_cells *cells)
-{
-    // The demod stage of a whole AFSK chain group in ONE call: the shared band-pass (afsk.py:151) and every certified sweep on its
-    // output (afsk.py:153-166, sign bitmaps only), overflow fallback deferred to the caller (pm_afsk_sweep_results).  The same
-    // launches pm_fir_valid_i16 + pm_afsk_sweep_signs[_tones] would make -- a pipelined Python host saves nine boundary crossings
-    // per recording, each of which waits for the interpreter lock on the way back.
-    PM_CTX(ctx);
-    PM_ARG(d_audio && d_bpf && d_bpf_out && h_sweeps && nsweeps >= 1 && nsweeps <= 64 && mb >= 1 && n >= mb);
-    static const bool trace = getenv("PM_TRACE_CALLS") != nullptr;
-    static double acc_us[3] = {0, 0, 0};
-    static long calls = 0;
-    const auto t_0 = std::chrono::steady_clock::now();
-    SweepSource src{d_audio, d_bpf, mb, plan ? pm_bpf8_error(plan) : 0.0};
-    PM_ARG(!cells || (cells->d_count && cells->h_mail));
-    if (plan) {
-        PM_ARG(pm_bpf8_taps(plan) == mb);
-        for (int k = 0; k < nsweeps; ++k) PM_ARG(h_sweeps[k].h_tones != nullptr);
-    }
-    if (plan && cells && cells->d_list) {
-        // one launch for the whole stage where the group qualifies (all sweeps on the matrix pipe, at most two): afsk_fused8_kernel
-        bool fused = false;
-        if (int rc = afsk_group_run_fused(ctx, d_audio, n, d_bpf, mb, x_bound, h_sweeps, nsweeps, plan, lpf8, cells, &fused)) return rc;
-        if (fused) return PM_OK;
-    }
-    if (plan) {
-        if (int rc = pm_bpf8_run(ctx, plan, d_audio, n, d_bpf_out, cells ? cells->d_count : nullptr, cells ? nsweeps : 0)) return rc;
-    } else {
-        if (cells) PM_HIP(hipMemsetAsync(cells->d_count, 0, sizeof(int) * (size_t)nsweeps, ctx->stream));
-        if (int rc = pm_fir_valid_i16(ctx, d_audio, n, d_bpf, mb, d_bpf_out, 0)) return rc;
-    }
-    const auto t_1 = std::chrono::steady_clock::now();
-    const bool was = ctx->sweep_deferred;
-    ctx->sweep_deferred = true;
-    int rc = PM_OK;
-    for (int k = 0; k < nsweeps && rc == PM_OK; ++k) {
-        const pm_afsk_sweep_desc &w = h_sweeps[k];
-        rc = sweep_signs(ctx, d_bpf_out, n - mb + 1, x_bound, w.d_mark_i, w.d_mark_q, w.d_unit_i, w.d_unit_q, w.d_space, w.h_gains, w.groups, w.m,
-                         w.d_lpf, w.ml, w.lpf_abs_sum, w.h_bits, w.h_tones, plan ? &src : nullptr, lpf8 ? lpf8[k] : nullptr,
-                         cells ? cells->d_count + k : nullptr, cells ? cells->h_mail + k : nullptr,
-                         cells && cells->d_list ? cells->d_list + (size_t)k * kSweepCap : nullptr);
-        if (h_tickets && !cells) h_tickets[k] = ctx->sweep_seq - 1;
-    }
-    ctx->sweep_deferred = was;
-    if (rc == PM_OK && cells && cells->d_list) {
-        // One wave behind the recording's last sweep leaves every sweep's count in its page-locked word (a sweep that ended with a launch
-        // of its own has written the same value there already).  Round 4 had a 4096-workgroup launch between and behind the sweeps for
-        // this and the recomputation: 0.23 ms per recording of the demod streams' time.
-        rc = sweep_mail_reset(ctx, cells, nsweeps);
-    }
-    if (trace) {
-        const auto t_2 = std::chrono::steady_clock::now();
-        acc_us[0] += std::chrono::duration<double, std::micro>(t_1 - t_0).count();
-        acc_us[1] += std::chrono::duration<double, std::micro>(t_2 - t_1).count();
-        if (++calls % 100 == 0) {
-            fprintf(stderr, "[pm_afsk_group_run] avg over 100 calls: band-pass launch %.1f us, %d sweeps %.1f us\n", acc_us[0] / 100, nsweeps, acc_us[1] / 100);
-            acc_us[0] = acc_us[1] = 0;
-        }
-    }
-    return rc;
-}
-
-int pm_afsk_sweep_exact_list(pm_ctx *ctx, const int16_t *d_audio, const double *d_bpf, int mb, const pm_afsk_sweep_desc *w, uint64_t *const *h_bits,
-                             const unsigned long long *d_list, const int *d_count)
-{
-    PM_CTX(ctx);
-    PM_ARG(d_audio && d_bpf && mb >= 1 && w && h_bits && d_list && d_count && w->groups >= 1 && w->groups <= kSweepMax);
-    SweepArgs P;
-    double gmax = 0.0;
-    PM_ARG(w->h_gains && sweep_args(w->h_gains, h_bits, w->groups, &P, &gmax));
-    PmProf prof(ctx, PM_K_SIGNS);
-    hipLaunchKernelGGL(sweep_exact_kernel<true>, dim3(kExactGrid), dim3(64), (size_t)(4 * w->ml + 6 * w->m + 2 * mb - 3) * sizeof(double), ctx->stream, (const double *)nullptr,
-                       w->d_mark_i, w->d_mark_q, w->d_space, w->m, w->d_lpf, w->ml, P, d_list, d_count, kSweepCap, (int *)nullptr, (int *)nullptr,
-                       SweepSource{d_audio, d_bpf, mb, 0.0});
-    PM_HIP(hipGetLastError());
-    return PM_OK;
-}
-
-extern "C" {
-
-int pm_afsk_sweep_mode(pm_ctx *ctx, int deferred)
-{
-    PM_ARG(ctx != nullptr);
-    ctx->sweep_deferred = deferred != 0;
     return PM_OK;
 }
 
@@ -1911,6 +1547,335 @@ int pm_afsk_sweep_result(pm_ctx *ctx, int64_t ticket, pm_ctx *via, int64_t *h_un
 }
 
 }  // extern "C"
+
+// ---- the launchers ----------------------------------------------------------------------------------------------------------------------------
+// one wave per uncertain decision at a time: as many workgroups as a sweep usually has entries (several hundred; an idle one costs a
+// dispatch slot for a microsecond), so that the launch lasts one entry's latency and not three
+constexpr int kExactGrid = 4096;
+
+// The exact chain over min(*count, kSweepCap) entries of a sweep's list: from the audio where the sweep's input was a value with a bound
+// (src.audio), else from d_x.  reset / mail: nullptr, or the words the launch clears / leaves the count in.
+static int sweep_exact_launch(pm_ctx *ctx, const double *d_x, const pm_afsk_sweep_desc &w, const SweepArgs &P, const SweepSource &src,
+                              const unsigned long long *list, const int *count, int *reset, int *mail)
+{
+    PmProf prof(ctx, PM_K_SIGNS);
+    if (src.audio)
+        hipLaunchKernelGGL(sweep_exact_kernel<true>, dim3(kExactGrid), dim3(64), sweep_tail_doubles(w.m, w.ml, src.mb) * sizeof(double), ctx->stream, d_x, w.d_mark_i,
+                           w.d_mark_q, w.d_space, w.m, w.d_lpf, w.ml, P, list, count, kSweepCap, reset, mail, src);
+    else
+        hipLaunchKernelGGL(sweep_exact_kernel<false>, dim3(kExactGrid), dim3(64), (size_t)w.ml * sizeof(double), ctx->stream, d_x, w.d_mark_i, w.d_mark_q, w.d_space,
+                           w.m, w.d_lpf, w.ml, P, list, count, kSweepCap, reset, mail, src);
+    PM_HIP(hipGetLastError());
+    return PM_OK;
+}
+
+// One certified sweep over d_x (n values).  deferred: the overflow fallback is the caller's (pm_afsk_sweep_mode), the three gated
+// launches at the end are not enqueued.  cells: nullptr (the context's ring) or the recording's own counters, sweep k of them.
+static int sweep_signs(pm_ctx *ctx, const double *d_x, int64_t n, double x_bound, const pm_afsk_sweep_desc &w, const SweepSource *src,
+                       const pm_lpf8_plan *lpf8, bool deferred, const pm_sweep_cells *cells = nullptr, int k = 0)
+{
+    PM_CTX(ctx);
+    // the gated exact launches read d_x and clear the ring's next slot: neither fits a stream with a source or a recording's own cells
+    PM_ARG(d_x && (deferred || (!src && !cells)));
+    SweepPlan S;
+    if (int rc = sweep_plan(ctx->tune, w, n, x_bound, src, lpf8, cells && cells->d_list, &S)) return rc;
+    const SweepRouting &R = S.R;
+    const int groups = w.groups, m = w.m, ml = w.ml;
+    const int64_t nc = S.nc, nl = S.nl;
+    const int cap = kSweepCap;                             // more uncertain samples than this: the gated exact path below takes over
+    const int F = 2 + 2 * groups;
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const int64_t stride = (nc + 63) / 64 * 64;
+    const size_t b_m = up((size_t)nc * 8), b_a = up((size_t)nl * 8), b_list = up((size_t)cap * 8), b_w = up((size_t)F * m * 8),
+                 b_c = up((size_t)stride * groups * 8);
+    if (int rc = pm_scratch_reserve(ctx, 2 * b_m + b_a + b_list + 256 + b_w + b_c)) return rc;
+    char *base = (char *)ctx->d_scratch;
+    double *M = (double *)base, *Sp = (double *)(base + b_m), *A = (double *)(base + 2 * b_m);
+    double *d_w = (double *)(base + 2 * b_m + b_a + b_list + 256);
+    double *C = (double *)(base + 2 * b_m + b_a + b_list + 256 + b_w);
+    // a recording's own cells (zeroed by an earlier launch on this stream, read by their owner when the stream has passed the sweep:
+    // the context's ring stays where it is), or the ring
+    SweepCounters cn{nullptr, nullptr, nullptr, nullptr};
+    if (cells) cn = SweepCounters{cells->d_count + k, nullptr, cells->h_mail + k, cells->d_list ? cells->d_list + (size_t)k * kSweepCap : nullptr};
+    else if (int rc = sweep_ring_take(ctx, deferred, &cn)) return rc;
+    if (!cn.list) cn.list = (unsigned long long *)(base + 2 * b_m + b_a);
+    RingGuard ring{ctx->stream, cn.next, false};
+    // Low-passes on the int8 matrix pipe from a plan of this call's own, for tests and measurements (PM_AFSK_LPF8=1)
+    pm_lpf8_plan *own8 = nullptr;
+    if (R.call_plan) {
+        std::vector<double> hl((size_t)ml);
+        PM_HIP(hipMemcpyAsync(hl.data(), w.d_lpf, hl.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        PM_HIP(hipStreamSynchronize(ctx->stream));
+        if (int rc = pm_lpf8_plan_create(ctx, hl.data(), ml, &own8)) return rc;
+    }
+    struct Own8 { pm_ctx *c; pm_lpf8_plan *p; ~Own8() { if (p) { (void)hipStreamSynchronize(c->stream); pm_lpf8_plan_destroy(p); } } } own8_guard{ctx, own8};
+    if (R.route == kFused64 || R.route == kFused8) {
+        // sliding sums, low-pass(es) and combine in one kernel: nothing but the bitmaps is written
+        const int64_t ntiles = pm_cdiv(nl, kTile);
+        PmProf prof(ctx, PM_K_FIR_F64);
+        prof.work((double)n * 8 + (double)groups * nl / 8,
+                  (4.0 * m / kFuseRun + 18.0) * (double)nc + (R.one ? 1.0 : 2.0) * 2.0 * ml * (double)nl + 2.0 * groups * (double)nl);
+        int rc;
+        if (R.route == kFused8) {
+            const Lpf8Args Q = own8 ? lpf8_args(own8, S.gmax, R.one) : S.Q;
+            const SweepShape shape{m, ml, R.one};
+            const Lpf8Layout Y = lpf8_layout(&shape, 1, S.src.mb, 0);
+            const SweepTail TL{w.d_space, w.d_lpf, R.lds_ok, S.src};
+            auto go8 = [&](auto kernel) -> int {
+                if (int rc = allow_lds(kernel, Y.lds)) return rc;
+                hipLaunchKernelGGL(kernel, dim3((unsigned)ntiles), dim3(kThreads), Y.lds, ctx->stream, d_x, n, w.d_mark_i, w.d_mark_q, w.d_unit_i, w.d_unit_q, m, S.T,
+                                   Q, ml, nl, groups, S.P, S.E, cn.list, cn.count, cap, Y.region0, TL);
+                return PM_OK;
+            };
+            rc = R.one ? go8(afsk_slide_lpf8_kernel<true>) : go8(afsk_slide_lpf8_kernel<false>);
+        } else {
+            const size_t lds = fuse_lds_bytes(m, ml);
+            const int region0 = (int)fuse_region0(m, ml), image = (int)fuse_image(ml);
+            auto go = [&](auto kernel) -> int {
+                if (int rc = allow_lds(kernel, lds)) return rc;
+                hipLaunchKernelGGL(kernel, dim3((unsigned)ntiles), dim3(kThreads), lds, ctx->stream, d_x, n, w.d_mark_i, w.d_mark_q, w.d_unit_i, w.d_unit_q, m, S.T,
+                                   w.d_lpf, ml, nl, groups, S.P, S.E, cn.list, cn.count, cap, region0, image);
+                return PM_OK;
+            };
+            rc = R.one ? go(afsk_slide_lpf_kernel<true, kFuseRun>) : go(afsk_slide_lpf_kernel<false, kFuseRun>);
+        }
+        if (rc) return rc;
+        PM_HIP(hipGetLastError());
+        if (R.ends) { ring.ok = true; return PM_OK; }      // nothing follows on this stream: the caller mails the count
+    } else {
+        // One chain with tone templates: its mark - gain * space difference leaves the sliding kernel as ONE stream and takes ONE
+        // low-pass (the reference's own dataflow, afsk.py:162-166, on approximate magnitudes); a sweep takes two for all its chains.
+        if (int rc = afsk_magnitudes(ctx, d_x, n, x_bound, w.d_mark_i, w.d_mark_q, w.d_unit_i, w.d_unit_q, m, w.h_tones, M, R.one ? nullptr : Sp, S.P.gain[0])) return rc;
+        if (!R.one)
+            if (int rc = pm_fir_valid_f64(ctx, M, nc, w.d_lpf, ml, A, 0)) return rc;
+        // B = LPF(S) and the combine step in one pass: B never reaches memory
+        const double *lp_in = R.one ? M : Sp, *lp_a = R.one ? nullptr : A;
+        constexpr int R8 = 8;
+        const int64_t ntiles = pm_cdiv(nl, (int64_t)kThreads * R8);
+        const size_t lds = lds_bytes<R8>(ml);
+        PmProf prof(ctx, PM_K_FIR_F64);
+        prof.work((double)nc * 8 + (R.one ? 0.0 : (double)nl * 8) + (double)groups * nl / 8, 2.0 * ml * (double)nl + 2.0 * groups * (double)nl);
+        auto go = [&](auto kernel) -> int {
+            if (int rc = allow_lds(kernel, lds)) return rc;
+            hipLaunchKernelGGL(kernel, dim3((unsigned)ntiles), dim3(kThreads), lds, ctx->stream, lp_in, nc, w.d_lpf, ml, lp_a, nl, groups, S.P, S.E, cn.list, cn.count, cap);
+            return PM_OK;
+        };
+        if (int rc = (((uintptr_t)lp_in) & 15) == 0 ? go(fir_sweep_kernel<R8, true>) : go(fir_sweep_kernel<R8, false>)) return rc;
+        PM_HIP(hipGetLastError());
+    }
+    // deferred: this is the sweep's last launch, which clears the next sweep's counter and mails its own
+    if (int rc = sweep_exact_launch(ctx, d_x, w, S.P, S.src, cn.list, cn.count, deferred ? cn.next : nullptr, cn.mail)) return rc;
+    // Deferred fallback: the caller looks at the counter once the sweep has finished (pm_afsk_sweep_result) and runs the exact
+    // chains itself in the (degenerate) overflow case; the three gated launches below -- which in the normal case only look at
+    // the counter and leave, but cost the demod stream three dispatches per sweep -- are not enqueued.
+    if (deferred) { ring.ok = true; return PM_OK; }
+    // More uncertain samples than the list holds (degenerate input: silence, amplitudes far below the caller's bound): the exact
+    // chain of every modem runs after all -- the same launches as pm_afsk_correlate_group + pm_fir_signs_f64_batch, each workgroup
+    // of which first looks at the counter and leaves at once in the normal case.  No host round trip either way.
+    hipLaunchKernelGGL(pack_group_taps_kernel, dim3((unsigned)pm_cdiv((int64_t)F * m, 256)), dim3(256), 0, ctx->stream, w.d_mark_i, w.d_mark_q,
+                       w.d_space, m, F, d_w);
+    if (int rc = afsk_group_dispatch(ctx, groups, d_x, n, d_w, m, C, stride, nc, cn.count, cap)) return rc;
+    const double *cx[kSweepMax];
+    int64_t cnn[kSweepMax];
+    for (int g = 0; g < groups; ++g) { cx[g] = C + (size_t)g * stride; cnn[g] = nc; }
+    if (int rc = pm_fir_signs_batch(ctx, groups, cx, cnn, w.d_lpf, ml, w.h_bits, 0, cn.count, cap, cn.next)) return rc;
+    ring.ok = true;
+    return PM_OK;
+}
+
+extern "C" {
+
+int pm_afsk_sweep_signs(pm_ctx *ctx, const double *d_x, int64_t n, double x_bound, const double *d_mark_i, const double *d_mark_q,
+                        const double *d_unit_i, const double *d_unit_q, const double *d_space, const double *h_gains, int groups, int m,
+                        const double *d_lpf, int ml, double lpf_abs_sum, uint64_t *const *h_bits)
+{
+    PM_ARG(ctx != nullptr);
+    const pm_afsk_sweep_desc w{d_mark_i, d_mark_q, d_unit_i, d_unit_q, d_space, h_gains, groups, m, d_lpf, ml, 0, lpf_abs_sum, h_bits, nullptr};
+    return sweep_signs(ctx, d_x, n, x_bound, w, nullptr, nullptr, ctx->sweep_deferred);
+}
+
+int pm_afsk_sweep_signs_tones(pm_ctx *ctx, const double *d_x, int64_t n, double x_bound, const double *d_mark_i, const double *d_mark_q,
+                              const double *d_unit_i, const double *d_unit_q, const double *d_space, const double *h_gains, int groups, int m,
+                              const double *d_lpf, int ml, double lpf_abs_sum, uint64_t *const *h_bits, const pm_afsk_tones *h_tones)
+{
+    if (!h_tones) return pm_set_error(PM_ERR_ARG, "pm_afsk_sweep_signs_tones: no tones");
+    PM_ARG(ctx != nullptr);
+    const pm_afsk_sweep_desc w{d_mark_i, d_mark_q, d_unit_i, d_unit_q, d_space, h_gains, groups, m, d_lpf, ml, 0, lpf_abs_sum, h_bits, h_tones};
+    return sweep_signs(ctx, d_x, n, x_bound, w, nullptr, nullptr, ctx->sweep_deferred);
+}
+
+int pm_afsk_magnitudes(pm_ctx *ctx, const double *d_x, int64_t n, double x_bound, const double *d_mark_i, const double *d_mark_q,
+                       const double *d_space_i, const double *d_space_q, int m, const pm_afsk_tones *h_tones, double *d_mark_mag,
+                       double *d_space_mag, double *h_bound)
+{
+    PM_CTX(ctx);
+    PM_ARG(d_x && d_mark_i && d_mark_q && d_space_i && d_space_q && d_mark_mag && d_space_mag);
+    PM_ARG(m >= 1 && m <= kMaxTaps && n >= m && x_bound > 0.0 && x_bound < 1e300);
+    if (int rc = afsk_magnitudes(ctx, d_x, n, x_bound, d_mark_i, d_mark_q, d_space_i, d_space_q, m, h_tones, d_mark_mag, d_space_mag)) return rc;
+    if (h_bound) *h_bound = h_tones && m >= 2 ? slide_bound(h_tones, m, x_bound) : 0.0;
+    return PM_OK;
+}
+
+int pm_afsk_group_run(pm_ctx *ctx, const int16_t *d_audio, int64_t n, const double *d_bpf, int mb, double *d_bpf_out, double x_bound,
+                      const pm_afsk_sweep_desc *h_sweeps, int nsweeps, int64_t *h_tickets)
+{
+    return pm_afsk_group_run_plan(ctx, d_audio, n, d_bpf, mb, d_bpf_out, x_bound, h_sweeps, nsweeps, h_tickets, nullptr, nullptr);
+}
+
+}  // extern "C"
+
+// The four templates of a sweep as ONE reversed, interleaved table (pack_group_taps_kernel's layout with F = 4), made the first time the
+// low-pass plan meets these templates and kept with it: afsk_fused8_kernel reads it through the scalar cache
+static int lpf8_plan_templates(pm_ctx *ctx, pm_lpf8_plan *q, const pm_afsk_sweep_desc &w)
+{
+    if (q->d_tpl && q->tpl_m == w.m && q->tpl_src[0] == w.d_mark_i && q->tpl_src[1] == w.d_mark_q && q->tpl_src[2] == w.d_unit_i && q->tpl_src[3] == w.d_unit_q)
+        return PM_OK;
+    if (q->d_tpl) { PM_HIP(hipStreamSynchronize(ctx->stream)); (void)hipFree(q->d_tpl); q->d_tpl = nullptr; }
+    PM_HIP(hipMalloc(&q->d_tpl, sizeof(double) * 4 * (size_t)w.m + 256));
+    hipLaunchKernelGGL(pack_templates_kernel, dim3((unsigned)pm_cdiv(4 * (int64_t)w.m, 256)), dim3(256), 0, ctx->stream, w.d_mark_i, w.d_mark_q, w.d_unit_i,
+                       w.d_unit_q, w.m, (double *)q->d_tpl);
+    PM_HIP(hipGetLastError());
+    PM_HIP(hipStreamSynchronize(ctx->stream));     // once per plan: another context's launch may be the table's next reader
+    q->tpl_m = w.m;
+    q->tpl_src[0] = w.d_mark_i; q->tpl_src[1] = w.d_mark_q; q->tpl_src[2] = w.d_unit_i; q->tpl_src[3] = w.d_unit_q;
+    return PM_OK;
+}
+
+// The fused launch of pm_afsk_group_run_plan (afsk_fused8_kernel), each sweep from its SweepPlan.  -> PM_OK and *fused = true when the
+// launch was made; *fused = false (and nothing enqueued) when the group does not qualify (group_fuses; a sweep that cannot be planned
+// does not) and the caller takes the split path, which plans each sweep again -- once more per recording, on that path only -- and
+// reports what is wrong with one that cannot be planned (sweep_plan has left the same message here already).
+static int afsk_group_run_fused(pm_ctx *ctx, const int16_t *d_audio, int64_t n, const double *d_bpf, int mb, double x_bound, const pm_afsk_sweep_desc *h_sweeps,
+                                int nsweeps, const pm_bpf8_plan *plan, const pm_lpf8_plan *const *lpf8, const pm_sweep_cells *cells, bool *fused)
+{
+    *fused = false;
+    int kb = 0;
+    const void *btab = nullptr;
+    double sc6[6];
+    // planned: a band-pass plan, the recording's own list, and one or two sweeps that each take the matrix pipe on a plan of the caller's
+    bool planned = plan && lpf8 && cells && cells->d_list && nsweeps <= 2 && pm_bpf8_plan_view(plan, &kb, &btab, sc6) == PM_OK;
+    const int64_t nb = n - mb + 1;
+    const SweepSource src{d_audio, d_bpf, mb, planned ? pm_bpf8_error(plan) : 0.0};      // the band-passed stream is a value within e_x of the reference's
+    SweepPlan pl[2];
+    SweepShape shape[2];
+    for (int k = 0; planned && k < nsweeps; ++k) {
+        shape[k] = SweepShape{h_sweeps[k].m, h_sweeps[k].ml, h_sweeps[k].groups == 1};
+        planned = lpf8[k] && sweep_plan(ctx->tune, h_sweeps[k], nb, x_bound, &src, lpf8[k], true, &pl[k]) == PM_OK && pl[k].R.route == kFused8;
+    }
+    const Lpf8Layout Y = planned ? lpf8_layout(shape, nsweeps, mb, kb) : Lpf8Layout{};
+    const SweepSwitches sw = sweep_switches(ctx->tune);
+    if (!group_fuses(Y, kb, planned, ((uintptr_t)d_audio & 15) == 0, sw)) return PM_OK;
+    FusedArgs A;
+    memset(&A, 0, sizeof(A));
+    for (int k = 0; k < nsweeps; ++k) {
+        const pm_afsk_sweep_desc &w = pl[k].w;
+        if (int rc = lpf8_plan_templates(ctx, const_cast<pm_lpf8_plan *>(lpf8[k]), w)) return rc;
+        FusedSweep &S = A.s[k];
+        S.mi = w.d_mark_i; S.mq = w.d_mark_q; S.ui = w.d_unit_i; S.uq = w.d_unit_q;
+        S.space = w.d_space; S.lpf = w.d_lpf;
+        S.tg = ctx->tune.sweep_lds_templates ? nullptr : (const double *)lpf8[k]->d_tpl;
+        S.m = w.m; S.ml = w.ml; S.G = w.groups;
+        S.one = pl[k].R.one;
+        S.P = pl[k].P;
+        S.T = pl[k].T;
+        S.E = pl[k].E;
+        S.Q = pl[k].Q;
+        S.list = cells->d_list + (size_t)k * kSweepCap;
+        S.count = cells->d_count + k;
+        S.nout = pl[k].nl;
+    }
+    A.audio = d_audio;
+    A.n = n;
+    A.nb = nb;
+    A.bp_btab = (const pm_bpf8_dev::i4 *)btab;
+    for (int i = 0; i < 5; ++i) A.sc.s[i] = sc6[i];
+    A.sc.c0 = sc6[5];
+    A.src = src;
+    A.xs_span = Y.xs_span; A.aplane = Y.aplane; A.mmax = Y.mmax;
+    A.xw_doubles = Y.xw_doubles; A.plane_bytes = Y.plane_bytes;
+    A.cap = kSweepCap;
+    A.lds_ok = Y.lds_ok && !sw.sweep_no_tail;
+    const size_t lds_launch = Y.lds + (size_t)std::max(0, ctx->tune.fused_lds_pad);      // (PM_FUSED_LDS_PAD: fewer workgroups per CU, to measure what occupancy is worth)
+    int64_t tiles = 0;
+    double bits_out = 0.0, flops = 2.0 * mb * (double)nb;
+    for (int k = 0; k < nsweeps; ++k) {
+        tiles = std::max(tiles, pm_cdiv(A.s[k].nout, (int64_t)kThreads * 8));
+        bits_out += (double)A.s[k].G * (double)A.s[k].nout / 8;
+        flops += (4.0 * A.s[k].m / kFuseRun + 18.0) * (double)(nb - A.s[k].m + 1) + (A.s[k].one ? 1.0 : 2.0) * 2.0 * A.s[k].ml * (double)A.s[k].nout +
+                 2.0 * A.s[k].G * (double)A.s[k].nout;
+    }
+    PM_ARG(tiles >= 1 && tiles < (1LL << 31));
+    {
+        PmProf prof(ctx, PM_K_FIR_F64);
+        prof.work((double)n * 2 + bits_out, flops);          // the recording in, the bitmaps out: nothing else crosses HBM
+        auto go = [&](auto kernel) -> int {
+            if (int rc = allow_lds(kernel, lds_launch)) return rc;
+            hipLaunchKernelGGL(kernel, dim3((unsigned)tiles), dim3(kThreads), lds_launch, ctx->stream, A);
+            return PM_OK;
+        };
+        int rc = PM_OK;
+        const bool o0 = A.s[0].one != 0, o1 = nsweeps == 2 && A.s[1].one != 0;
+#define PM_FUSED_GO(KB)                                                                                                             \
+        rc = nsweeps == 1 ? (o0 ? go(afsk_fused8_kernel<KB, true, 1, false>) : go(afsk_fused8_kernel<KB, false, 1, false>))              \
+                          : (o0 ? (o1 ? go(afsk_fused8_kernel<KB, true, 2, true>) : go(afsk_fused8_kernel<KB, true, 2, false>))          \
+                                : (o1 ? go(afsk_fused8_kernel<KB, false, 2, true>) : go(afsk_fused8_kernel<KB, false, 2, false>)));
+        if (kb == 3) { PM_FUSED_GO(3) } else { PM_FUSED_GO(4) }
+#undef PM_FUSED_GO
+        if (rc) return rc;
+        PM_HIP(hipGetLastError());
+    }
+    if (int rc = sweep_mail_reset(ctx, cells, nsweeps)) return rc;
+    *fused = true;
+    return PM_OK;
+}
+
+int pm_afsk_group_run_plan(pm_ctx *ctx, const int16_t *d_audio, int64_t n, const double *d_bpf, int mb, double *d_bpf_out, double x_bound,
+                           const pm_afsk_sweep_desc *h_sweeps, int nsweeps, int64_t *h_tickets, const pm_bpf8_plan *plan,
+                           const pm_lpf8_plan *const *lpf8, const pm_sweep_cells *cells)
+{
+    // The demod stage of a whole AFSK chain group in ONE call: the shared band-pass (afsk.py:151) and every certified sweep on its
+    // output (afsk.py:153-166, sign bitmaps only), overflow fallback deferred to the caller (pm_afsk_sweep_results).  The same
+    // launches pm_fir_valid_i16 + pm_afsk_sweep_signs[_tones] would make -- a pipelined Python host saves nine boundary crossings
+    // per recording, each of which waits for the interpreter lock on the way back.
+    PM_CTX(ctx);
+    PM_ARG(d_audio && d_bpf && d_bpf_out && h_sweeps && nsweeps >= 1 && nsweeps <= 64 && mb >= 1 && n >= mb);
+    const SweepSource src{d_audio, d_bpf, mb, plan ? pm_bpf8_error(plan) : 0.0};
+    PM_ARG(!cells || (cells->d_count && cells->h_mail));
+    if (plan) {
+        PM_ARG(pm_bpf8_taps(plan) == mb);
+        for (int k = 0; k < nsweeps; ++k) PM_ARG(h_sweeps[k].h_tones != nullptr);
+    }
+    // one launch for the whole stage where the group qualifies (all sweeps on the matrix pipe, at most two): afsk_fused8_kernel
+    bool fused = false;
+    if (int rc = afsk_group_run_fused(ctx, d_audio, n, d_bpf, mb, x_bound, h_sweeps, nsweeps, plan, lpf8, cells, &fused)) return rc;
+    if (fused) return PM_OK;
+    if (plan) {
+        if (int rc = pm_bpf8_run(ctx, plan, d_audio, n, d_bpf_out, cells ? cells->d_count : nullptr, cells ? nsweeps : 0)) return rc;
+    } else {
+        if (cells) PM_HIP(hipMemsetAsync(cells->d_count, 0, sizeof(int) * (size_t)nsweeps, ctx->stream));
+        if (int rc = pm_fir_valid_i16(ctx, d_audio, n, d_bpf, mb, d_bpf_out, 0)) return rc;
+    }
+    for (int k = 0; k < nsweeps; ++k) {
+        if (int rc = sweep_signs(ctx, d_bpf_out, n - mb + 1, x_bound, h_sweeps[k], plan ? &src : nullptr, lpf8 ? lpf8[k] : nullptr, true, cells, k)) return rc;
+        if (h_tickets && !cells) h_tickets[k] = ctx->sweep_seq - 1;
+    }
+    // One wave behind the recording's last sweep leaves every sweep's count in its page-locked word (a sweep that ended with a launch
+    // of its own has written the same value there already): no launch between the sweeps for this or for the recomputation
+    if (cells && cells->d_list) return sweep_mail_reset(ctx, cells, nsweeps);
+    return PM_OK;
+}
+
+int pm_afsk_sweep_exact_list(pm_ctx *ctx, const int16_t *d_audio, const double *d_bpf, int mb, const pm_afsk_sweep_desc *w, uint64_t *const *h_bits,
+                             const unsigned long long *d_list, const int *d_count)
+{
+    PM_CTX(ctx);
+    // (not through sweep_plan: whoever works a list off has neither the stream's length nor its bound, and brings the bitmaps apart)
+    PM_ARG(d_audio && d_bpf && mb >= 1 && w && h_bits && d_list && d_count && w->groups >= 1 && w->groups <= kSweepMax);
+    SweepArgs P;
+    double gmax = 0.0;
+    PM_ARG(w->h_gains && sweep_args(w->h_gains, h_bits, w->groups, &P, &gmax));
+    return sweep_exact_launch(ctx, nullptr, *w, P, SweepSource{d_audio, d_bpf, mb, 0.0}, d_list, d_count, nullptr, nullptr);
+}
 
 // int8 digit products per tap and output of the matrix-pipe kernels, from the kernels' own constants (bench.py prices the launches with them)
 extern "C" int pm_matrix_digit_pairs(int stage)

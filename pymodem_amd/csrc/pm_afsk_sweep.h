@@ -1,6 +1,7 @@
-// The host arithmetic a certified AFSK sweep's decision rests on (pm_afsk.hip), in ONE copy: the bound E, the matrix-pipe constants and
-// the dynamic-LDS layout of afsk_slide_lpf8_kernel / afsk_fused8_kernel.  Plain C++17, no HIP types: tests/afsk_sweep_core_check.cpp
-// checks it on the host -- a wrong E or layout fails no bitmap test, only the count of uncertain samples or the launch path moves.
+// The host arithmetic a certified AFSK sweep's decision rests on (pm_afsk.hip), in ONE copy: the bound E, the matrix-pipe constants, the
+// dynamic-LDS layouts of afsk_slide_lpf_kernel / afsk_slide_lpf8_kernel / afsk_fused8_kernel and the choice of the launch a sweep takes.
+// Plain C++17, no HIP types: tests/afsk_sweep_core_check.cpp checks it on the host -- a wrong E, layout or route fails no bitmap test,
+// only the count of uncertain samples or the launch path moves.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -53,7 +54,7 @@ struct Lpf8Consts {
 static inline Lpf8Consts lpf8_consts(int S, double tapq_int, double qabs, double dlow, double gmax, bool one) { return Lpf8Consts{S, tapq_int, 0.5 * qabs + dlow, one ? 1.0 : 1.0 + gmax, qabs}; }
 
 // sliding runs of a workgroup: it needs the ml - 1 magnitudes past its kTile outputs too
-static inline int sweep_runs(int ml, int L = kFuseRun) { return (kTile + ml - 1 + L - 1) / L; }
+static inline int sweep_runs(int ml) { return (kTile + ml - 1 + kFuseRun - 1) / kFuseRun; }
 // doubles of LDS the exact chain of one (sample, modem) pair works in (sweep_tail_entry)
 static inline size_t sweep_tail_doubles(int mc, int ml, int mb) { return (size_t)2 * ml + (size_t)(ml + mc - 1) * 2 + 2 * (size_t)mb + 4 * (size_t)mc; }
 
@@ -99,6 +100,54 @@ static inline Lpf8Layout lpf8_layout(const SweepShape *s, int nsweeps, int mb, i
     Y.lds_ok = tail <= (size_t)Y.region0;
     Y.fuses = Y.fuses && Y.lds <= 64 * 1024;
     return Y;
+}
+
+// The dynamic LDS block of afsk_slide_lpf_kernel (low-passes in binary64):  window of x, later the space image | mark image | templates.
+// The window in slide_slot's layout (a pad slot per run), the images in the FIR's (slot<8>(p) = p + p / 8).
+static inline size_t fuse_region0(int m, int ml)
+{
+    const int nmag = kTile + ml - 1, p = sweep_runs(ml) * kFuseRun + m - 1;
+    const int a = p + p / kFuseRun + 2, b = nmag + nmag / 8 + 2;
+    return (size_t)(std::max(a, b) + 1) / 2 * 2;
+}
+static inline size_t fuse_image(int ml) { return (size_t)(kTile + ml - 1 + (kTile + ml - 1) / 8 + 3) / 2 * 2; }
+static inline size_t fuse_lds_bytes(int m, int ml) { return (fuse_region0(m, ml) + fuse_image(ml) + 4 * (size_t)m) * sizeof(double); }
+
+// ---- which launch a sweep takes -----------------------------------------------------------------------------------------------------
+// kDirect: direct correlator sums, two low-passes, fir_sweep_kernel.  kSlide: sliding sums (afsk_slide_kernel) in front of the same.
+// kFused64: afsk_slide_lpf_kernel.  kFused8: afsk_slide_lpf8_kernel, the low-passes on the matrix pipe.
+enum SweepRoute { kDirect, kSlide, kFused64, kFused8 };
+struct SweepSwitches { bool afsk_unfused, afsk_lpf8, sweep_no_tail, afsk_split; };      // pm_tuning's, as the launchers read them
+struct SweepRouting {
+    SweepRoute route;
+    bool one;                            // one chain with tone templates: its mark - gain * space difference is ONE stream with ONE low-pass
+    bool call_plan;                      // kFused8 on a low-pass plan made for this call (afsk_lpf8), not the caller's
+    bool lds_ok;                         // kFused8: the workgroups decide their own uncertain samples (SweepTail::lds_ok)
+    bool ends;                           // the sweep's own launch is its last: no exact launch behind it, the caller mails the count
+};
+// tones: the templates are tone models (sliding sums apply); mb: band-pass taps of the source the exact chain goes back to (0: none);
+// plan_ml: taps of the caller's low-pass plan (0: none); own_list: the recording's own list (pm_sweep_cells::d_list)
+static inline SweepRouting sweep_route(int m, int ml, int groups, bool tones, int mb, int plan_ml, bool own_list, const SweepSwitches &sw)
+{
+    const bool slide = tones && m >= 2;
+    SweepRouting R{slide ? kSlide : kDirect, slide && groups == 1, false, false, false};
+    if (!slide || sweep_runs(ml) > kLanes || fuse_lds_bytes(m, ml) > 120 * 1024 || sw.afsk_unfused) return R;
+    R.route = kFused64;
+    R.call_plan = plan_ml == 0 && sw.afsk_lpf8;
+    if (ml + 15 > 128 || !(R.call_plan || plan_ml == ml)) { R.call_plan = false; return R; }
+    R.route = kFused8;
+    const SweepShape shape{m, ml, R.one};
+    R.lds_ok = lpf8_layout(&shape, 1, mb, 0).lds_ok && !sw.sweep_no_tail;
+    R.ends = own_list;
+    return R;
+}
+
+// A recording's whole demod stage as afsk_fused8_kernel's single launch.  planned: a band-pass plan (of kb blocks), the recording's own
+// list, and one or two sweeps that each take kFused8 on a plan of the caller's (which afsk_unfused rules out); aligned: the audio is on
+// a 16-byte boundary; Y: lpf8_layout of the group, a layout the kernel is written for; and afsk_split does not ask for the launches apart.
+static inline bool group_fuses(const Lpf8Layout &Y, int kb, bool planned, bool aligned, const SweepSwitches &sw)
+{
+    return planned && aligned && (kb == 3 || kb == 4) && !sw.afsk_split && Y.fuses;
 }
 
 }  // namespace pm_sweep

@@ -28,7 +28,6 @@ struct pm_sweep_cells {
 // pm_runtime.hip), or set per context with pm_ctx_tune -- no launch path calls getenv.  README.md lists what each one is for.
 struct pm_tuning {
     int fir_no_short = 0;              // PM_FIR_NO_SHORT: short-tap sign FIR through the LDS kernel
-    int fuse_run = 0;                  // PM_FUSE_RUN: 16 = round 1's run length in the fused AFSK kernel (0: the default)
     int afsk_unfused = 0;              // PM_AFSK_UNFUSED: certified AFSK path as separate kernels
     int afsk_lpf8 = 0;                 // PM_AFSK_LPF8: pm_afsk_sweep_signs_tones with a per-call matrix-pipe low-pass plan
     int loop_wide = -1;                // PM_LOOP_WIDE: carrier-loop kernel shape 0 / 1 / 2 (-1: by size)

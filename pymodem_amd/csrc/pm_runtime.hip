@@ -20,7 +20,7 @@ int pm_set_error(int code, const char *fmt, ...)
 namespace {
 struct TuneKey { const char *name, *env; int pm_tuning::*field; };
 const TuneKey kTuneKeys[] = {
-    {"fir_no_short", "PM_FIR_NO_SHORT", &pm_tuning::fir_no_short}, {"fuse_run", "PM_FUSE_RUN", &pm_tuning::fuse_run},
+    {"fir_no_short", "PM_FIR_NO_SHORT", &pm_tuning::fir_no_short},
     {"afsk_unfused", "PM_AFSK_UNFUSED", &pm_tuning::afsk_unfused}, {"afsk_lpf8", "PM_AFSK_LPF8", &pm_tuning::afsk_lpf8},
     {"loop_wide", "PM_LOOP_WIDE", &pm_tuning::loop_wide}, {"lbatch_tail", "PM_LBATCH_TAIL", &pm_tuning::lbatch_tail},
     {"agc_trace", "PM_AGC_TRACE", &pm_tuning::agc_trace},

@@ -1,9 +1,9 @@
 """The host arithmetic the certified AFSK sweeps' decision rests on (csrc/pm_afsk_sweep.h) without a GPU: afsk_sweep_core_check.cpp
-evaluates the bound E, the matrix-pipe constants and the dynamic-LDS layout of the two matrix-pipe kernels for the headline config's
-two sweeps, the 8 kHz / 300 baud shape of test_one_chain_certified_signs_are_the_exact_chain_s and the edges (ml = 113 / 114, m = 2,
+evaluates the bound E, the matrix-pipe constants, the dynamic-LDS layouts of the fused kernels and the route -- which launch a sweep,
+and a group of sweeps, takes -- for the headline config's two sweeps, the 8 kHz / 300 baud shape of test_one_chain_certified_signs_are_the_exact_chain_s and the edges (ml = 113 / 114, m = 2,
 long correlators), and every number must be the one recorded in golden/afsk_sweep_core.json from the expressions the launchers
 carried before they shared this header (its "about" says how).  A wrong E or layout fails no bitmap test: the bitmaps stay the
-oracle's and only the count of uncertain samples, or the launch path, moves."""
+oracle's and only the count of uncertain samples, or the launch path, moves; the same holds for every condition of the route."""
 import json
 import os
 import shutil
@@ -15,6 +15,9 @@ import pytest
 from conftest import GOLDEN, ROOT
 
 CASE_KEYS = ("name", "m", "ml", "mb", "kb", "one", "gmax", "lpf_abs_sum", "x_bound", "tap_dev", "e_x", "S", "tapq_int", "qabs", "dlow")
+GROUP_KEYS = ("planned", "aligned", "afsk_split")
+ROUTE_KEYS = ("name", "m", "ml", "groups", "tones", "mb", "plan_ml", "own_list", "afsk_unfused", "afsk_lpf8", "sweep_no_tail")
+DIRECT, SLIDE, FUSED64, FUSED8 = range(4)                      # pm_sweep::SweepRoute
 BAND, LIST, MAXIMA = 2 * 3 * 64 * 16, (48 + 4) * 4, 32        # bytes behind the templates: band operands, workgroup list, wave maxima
 
 
@@ -35,7 +38,9 @@ def got(tmp_path_factory, golden):
                            os.path.join(ROOT, "tests", "afsk_sweep_core_check.cpp"), "-o", str(exe)])
     lines = [str(len(golden["cases"]))] + [" ".join(str(c[k]) for k in CASE_KEYS) for c in golden["cases"]]
     lines += [str(len(golden["groups"]))]
-    lines += [f"{g['name']} {g['kb']} {g['mb']} {len(g['sweeps'])} " + " ".join(f"{m} {ml} {one}" for m, ml, one in g["sweeps"]) for g in golden["groups"]]
+    lines += [f"{g['name']} {g['kb']} {g['mb']} {len(g['sweeps'])} " + " ".join(f"{m} {ml} {one}" for m, ml, one in g["sweeps"]) + " " +
+              " ".join(str(g[k]) for k in GROUP_KEYS) for g in golden["groups"]]
+    lines += [str(len(golden["routes"]))] + [" ".join(str(r[k]) for k in ROUTE_KEYS) for r in golden["routes"]]
     (d / "cases.txt").write_text("\n".join(lines) + "\n")
     run = subprocess.run([str(exe), str(d / "cases.txt")], capture_output=True, text=True)
     assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-2000:]
@@ -154,3 +159,81 @@ def test_the_headline_group_takes_the_fused_launch(golden, got):
         assert int(got[name]["fuses"]) == 1 and int(got[name]["lds"]) <= 64 * 1024 and int(got[name]["lds_ok"]) == 1
     assert int(got["group_ml113"]["fuses"]) == 1 and int(got["group_ml114"]["fuses"]) == 0
     assert int(got["group_ml114"]["lds"]) <= 64 * 1024, "it is the low-pass length that refuses ml = 114, not the LDS"
+
+
+def test_the_fused_binary64_kernels_lds_holds_together(golden, got):
+    """afsk_slide_lpf_kernel's block: the window of x in runs of 12 with a pad slot each (later the space image), the mark image in
+    the FIR's padded layout, four templates."""
+    for c in golden["cases"]:
+        L = got[c["name"]]
+        nmag = 2048 + c["ml"] - 1
+        window = int(L["runs"]) * 12 + c["m"] - 1
+        image = nmag + nmag // 8
+        assert int(L["fuse_image"]) % 2 == 0 and image + 2 <= int(L["fuse_image"]) <= image + 3, c["name"]
+        assert int(L["fuse_region0"]) % 2 == 0 and 0 <= int(L["fuse_region0"]) - max(window + window // 12 + 2, image + 2) <= 1, c["name"]
+        assert int(L["fuse_lds"]) == 8 * (int(L["fuse_region0"]) + int(L["fuse_image"]) + 4 * c["m"]), c["name"]
+
+
+def test_every_route_and_both_outcomes_of_every_condition_occur(golden, got):
+    """The recorded routes (test_every_number_is_the_one_the_launchers_computed compares them) cover the launchers' whole decision:
+    each case below names the one condition that sends it where it goes."""
+    R = {r["name"]: {k: int(v) for k, v in got[r["name"]].items()} for r in golden["routes"]}
+    assert {x["route"] for x in R.values()} == {DIRECT, SLIDE, FUSED64, FUSED8}
+    for key in ("one", "call_plan", "lds_ok", "ends"):
+        assert {x[key] for x in R.values()} == {0, 1}, key
+    where = {"direct_no_tones": DIRECT, "direct_one_group_no_tones": DIRECT, "direct_m1": DIRECT,            # no tone templates; m == 1
+             "slide_lpf_1026": SLIDE, "fused64_lpf_1025": FUSED64,                                            # sweep_runs(ml) > 256 or not
+             "slide_m2200": SLIDE, "fused64_m2000": FUSED64,                                                  # more than 120 KiB of LDS or not
+             "slide_unfused": SLIDE, "slide_unfused_planned": SLIDE, "fused64_plain": FUSED64,                # afsk_unfused
+             "fused8_call_plan": FUSED8, "fused64_call_plan_ml114": FUSED64,                                  # afsk_lpf8, and ml + 15 <= 128
+             "fused64_plan_other_ml": FUSED64, "fused64_plan_other_ml_lpf8_switch": FUSED64,                  # a plan of another length
+             "route_ml113": FUSED8, "route_ml114": FUSED64, "fused8_ring": FUSED8}
+    for name, route in where.items():
+        assert R[name]["route"] == route, name
+    by = {r["name"]: r for r in golden["routes"]}
+    assert by["slide_lpf_1026"]["ml"] - by["fused64_lpf_1025"]["ml"] == 1 and -(-(2048 + 1025 - 1) // 12) == 256      # a run per lane at most
+
+    def fuse_lds(m, ml):
+        nmag, window = 2048 + ml - 1, -(-(2048 + ml - 1) // 12) * 12 + m - 1
+        even = lambda v: (v + 1) // 2 * 2
+        return 8 * (even(max(window + window // 12 + 2, nmag + nmag // 8 + 2)) + even(nmag + nmag // 8 + 2) + 4 * m)
+    assert fuse_lds(by["fused64_m2000"]["m"], 100) <= 120 * 1024 < fuse_lds(by["slide_m2200"]["m"], 100)
+    # one stream: one chain AND sliding sums
+    assert R["fused64_one"]["one"] and R["slide_unfused_one"]["one"] and not R["direct_one_group_no_tones"]["one"] and not R["direct_m1"]["one"]
+    assert not R["fused64_plain"]["one"]
+    # the call's own plan only where the matrix pipe takes the sweep and the caller brought none
+    assert R["fused8_call_plan"]["call_plan"] and not R["fused64_call_plan_ml114"]["call_plan"] and not R["fused64_plan_other_ml_lpf8_switch"]["call_plan"]
+    assert not R["direct_no_tones_lpf8_switch"]["call_plan"] and not R["route_headline_seven"]["call_plan"]
+    # the workgroups' own exact chain: the layout's room, and sweep_no_tail
+    assert R["fused8_ring"]["lds_ok"] and not R["fused8_no_tail"]["lds_ok"] and not R["route_m400"]["lds_ok"] and not R["fused8_m400_no_source"]["lds_ok"]
+    for r in golden["routes"]:
+        x = R[r["name"]]
+        # no launch behind the sweep: the matrix pipe with the recording's own list, nothing else
+        assert x["ends"] == int(x["route"] == FUSED8 and r["own_list"] == 1), r["name"]
+        assert x["route"] == FUSED8 or not (x["lds_ok"] or x["call_plan"]), r["name"]
+        assert x["route"] >= SLIDE or not x["one"], r["name"]
+
+
+def test_a_sweeps_route_agrees_with_its_layout(golden, got):
+    """lds_ok of a matrix-pipe sweep is the split kernel's layout's (with the band-pass taps of its source) unless sweep_no_tail."""
+    for c in golden["cases"]:
+        x = got["route_" + c["name"]]
+        if int(x["route"]) == FUSED8:
+            assert int(x["lds_ok"]) == int(got[c["name"]]["sp_lds_ok"]), c["name"]
+
+
+def test_the_group_launch_needs_every_condition(golden, got):
+    """group_fuses: the layout's verdict and nothing that asks for the launches apart -- every condition refuses at least one group
+    that would otherwise take the single launch."""
+    takes = {g["name"]: int(got[g["name"]]["takes"]) for g in golden["groups"]}
+    for g in golden["groups"]:
+        plain = g["planned"] and g["aligned"] and not g["afsk_split"] and g["kb"] in (3, 4)
+        assert takes[g["name"]] == int(bool(plain) and int(got[g["name"]]["fuses"]) == 1), g["name"]
+    assert takes["group_headline"] == takes["group_headline_swapped"] == takes["group_headline_kb4"] == 1
+    for name in ("group_unplanned", "group_unaligned", "group_split", "group_kb5", "group_ml114", "group_m1000"):
+        assert takes[name] == 0, name
+    for name in ("group_unplanned", "group_unaligned", "group_split"):
+        assert int(got[name]["fuses"]) == 1, name + ": it is the named condition that refuses it, not the layout"
+    # the headline's sweeps, as the pipeline submits them, each take the matrix pipe and end without a launch of their own
+    for name in ("route_headline_one", "route_headline_seven"):
+        assert (int(got[name]["route"]), int(got[name]["lds_ok"]), int(got[name]["ends"])) == (FUSED8, 1, 1), name

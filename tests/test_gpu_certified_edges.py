@@ -5,7 +5,9 @@ a proven bound E, every output with |value| <= E recomputed in the canonical ord
     bit for bit, which outputs the kernel must flag): the bits are the canonical sum's and `h_recomputed` is the model's count exactly;
   * the AFSK gain sweeps of the headline config on audio that dwells at each chain's tie LPF(M) = g LPF(S): the oracle's own stream has
     samples inside the combine bound, every mode's bits are the oracle's and its counter sees at least those samples;
-  * int16 -32768 (and 32767) through the native executor at the fused launch's tile edges."""
+  * int16 -32768 (and 32767) through the native executor at the fused launch's tile edges;
+  * exact zeros at the first and last outputs of a stream through the executor: the exact chain from the audio, in the workgroup and
+    from the recording's list."""
 import ctypes
 import json
 import os
@@ -210,3 +212,52 @@ def test_both_rails_through_the_executor_at_the_tile_edges():
                 assert not got[len(want):].any(), (k, c)
             pipe.release(tk)
     pipe.close()
+
+
+def test_uncertain_samples_at_the_ends_of_a_stream_through_the_executor():
+    """The exact chain from the audio at a stream's first and last outputs.  The signal of
+    test_both_rails_through_the_executor_at_the_tile_edges over two tiles and a bit, digital silence at both ends: the first and the
+    last outputs of every chain are exact zeros, which no bound certifies, and each sweep has (sample, chain) pairs inside 0.99
+    E_combine -- at most a sixteenth of the 65536-entry list, so the list path cannot turn into the overflow path (on the oracle: 180
+    pairs for the lone chain, 130 to 132 for each of the other seven).  They are decided in the workgroup that found them, and -- with
+    sweep_no_tail -- from the recording's list (pm_afsk_sweep_exact_list), behind the single fused launch and behind one launch per
+    sweep: every chain's bitmap (nothing set past its last bit), slicer bytes and addresses are the oracle's."""
+    import pymodem_amd
+    from pymodem_amd import chain_builder as cb, chain_execute as ce
+    lines = _lines()
+    sweeps = _sweeps(lines)
+    bpf, lpf = sweeps[0][5], sweeps[0][4]
+    least = len(bpf) + max(m for *_, m in sweeps) + len(lpf) - 2
+    n = least + 2 * 2048 + 200
+    assert (least, n) == (306, 4602)
+    rng = np.random.default_rng(32768)
+    t = np.arange(n)
+    x = 60000.0 * np.sin(2 * np.pi * np.where((t // 40) % 2 == 0, 1300.0, 2100.0).cumsum() / 48000.0) + 20000.0 * rng.standard_normal(n)
+    audio = np.clip(np.rint(x), -32768, 32767).astype(np.int16)
+    audio[: least + 64] = 0
+    audio[-(least + 64):] = 0
+    want = [O.run_chain(O.build_chain(48000, l), audio, canon=True) for l in lines]
+    for chains, gains, mark, unit, lpf, bpf, m in sweeps:
+        E, _ = _e_combine(lpf, bpf, gains, m)
+        pairs = 0
+        for c in chains:
+            y = np.asarray(want[c]["demod"])
+            assert y[0] == 0.0 and y[-1] == 0.0, c
+            pairs += int(np.count_nonzero(np.abs(y) <= 0.99 * E))
+        assert 1 <= pairs <= 4096, (chains, pairs)
+    ctx = pymodem_amd.Context.default()
+    d = ctx.upload(audio)
+    ctx.sync()
+    for switches in ({}, {"sweep_no_tail": 1}, {"afsk_split": 1, "sweep_no_tail": 1}):
+        with tuned(ctx, **switches):
+            pipe = ce.NativePipeline([cb.build_chain(48000, l) for l in lines], n, 48000 / 40, ctx=ctx, keep_slices=True)   # its demod contexts copy the switches
+            tk = pipe.submit(d)
+            for c, w in enumerate(want):
+                sliced, _ = pipe.slices(tk, c)
+                wb = np.asarray(w["demod"]) >= 0
+                got = pipe.bitmap(tk, c, (len(wb) + 63) // 64 * 64)
+                assert np.array_equal(got[: len(wb)], wb), (switches, c, int(np.count_nonzero(got[: len(wb)] != wb)))
+                assert not got[len(wb):].any(), (switches, c)
+                assert np.array_equal(sliced.data, w["slice_data"]) and np.array_equal(sliced.address, w["slice_addr"]), (switches, c)
+            pipe.release(tk)
+            pipe.close()
