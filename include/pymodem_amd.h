@@ -660,6 +660,56 @@ int pm_rows_carry_start(pm_ctx *ctx, pm_rows_carry *d_carries, int64_t row0, int
 int pm_rows_scan_pieces(pm_ctx *ctx, const pm_rowslice_rec *d_recs, const uint8_t *d_data, const uint16_t *d_steps, int64_t cap, int64_t row0, int nrows,
                         const pm_rows_scan_chain *h_chains, int nchains, pm_rows_carry *d_carries, const int64_t *d_upto, int32_t final,
                         const int64_t *h_counts, void *d_block, size_t block_bytes, int64_t *h_offsets, size_t *h_used);
+/* MARKS: a sliced run that says, chunk by chunk, how far every row has got -- what pm_rows_scan_pieces' d_upto is shaped for, so that the
+ * rows of a run can be taken and decoded BESIDE the run instead of behind it.  A pm_lbatch_marks object (made for one engine and up to
+ * max_chunks chunks; destroy it before the engine) holds for each chunk t of a run:
+ *   - an int64 per row in device memory (8-byte aligned, mark t's row r at index t * rows + r, rows = recordings * chains of that run):
+ *     min(count, cap) of the row's record as it stood when the row slicers of chunk t were through;
+ *   - the same values in page-locked host memory;
+ *   - one int32 with the OR of the rows' flags at that point (page-locked host memory; non-zero: a row has outgrown its room or its 16-bit
+ *     steps and the run is to be redone the other way, as pm_rowslice_rec.flags says at the end);
+ *   - one event (hipEventDisableTiming), recorded on the slicers' stream behind all of it.
+ * pm_lbatch_run_sliced_marked is pm_lbatch_run_sliced with such an object: directly behind the row slicers of chunk t, on their stream, one
+ * more small launch (a lane a row, plain vector stores to both copies; the flags OR-ed over the wave and by one lane a wave into the chunk's
+ * word, which a memset on the same stream cleared when the run began), a four-byte copy of the word to the host, and the event.  The run's
+ * own launches, streams and results are those of pm_lbatch_run_sliced, byte for byte; the engine never waits for a reader, let alone for the
+ * host.  *h_chunks: the run's chunk count.  PM_ERR_CAPACITY, with nothing enqueued, for a run of more than max_chunks chunks.
+ * pm_lbatch_run_sliced itself enqueues exactly what it did before marks existed.  A marks object serves one run at a time: the next marked
+ * run with it overwrites the marks (its caller is through with the previous run's, as with d_data, d_steps and d_recs).
+ *
+ * Readers.  Every one of them refuses (PM_ERR_ARG) a t below 0 or at or beyond the chunk count of the last marked call that SUCCEEDED with
+ * this object; while a marked call is being made and after one that failed that count is 0.  So no reader can wait for an event that no
+ * call has recorded -- such a wait would never end.
+ *   pm_lbatch_marks_ready    no waiting (hipEventQuery): *h_latest = the newest mark whose event has completed, -1 if none.
+ *   pm_lbatch_marks_wait     host wait for mark t as pm_event_sync_relaxed waits (polls every poll_us microseconds); mark t's host copies
+ *                            may be read afterwards.
+ *   pm_lbatch_marks_wait_on  what is submitted to ctx from now on waits, on the GPU, for mark t (hipStreamWaitEvent).
+ *   pm_lbatch_marks_view     mark t's pointers (any of the three may be NULL): the rows' int64 on the device and on the host, the flag word.
+ *
+ * Reading rows under a running engine.  A piece taken at mark t (pm_rows_scan_pieces with d_upto = mark t's device values + row0, on a
+ * context that did pm_lbatch_marks_wait_on(t) first) runs while the row slicers of chunks t + 1 ... write the same rows and records.  That is
+ * sound without any further synchronisation, because of what is written and what is read:
+ *   - the row slicers store a data byte and its step only at index `count` and above (count itself grows behind the store), so every byte
+ *     and step below a mark is final when the mark is made;
+ *   - mark t's event orders those stores, and the mark's own, in front of everything on a stream that waited for it;
+ *   - the piece launches read two fields of a record and no others, both in the prepare launch: count and first_addr (the launches behind
+ *     it take the address in front of the piece from the prepare launch's table);
+ *   - count only grows and is only ever compared against d_upto: with a mark below it the piece is the mark's, whatever count says by then;
+ *   - first_addr is final once count >= 1 (later chunks store the same value again) and is used only while the carry's taken == 0, for a
+ *     piece that then either has d_upto >= 1 -- the value was final at the mark -- or is empty and has no address;
+ *   - last_addr never comes from the record: it is the carry's (pm_rows_carry.last_addr), which only the pieces write.
+ * The bytes between the mark and the moving count are simply not looked at.  The records as a whole (end states, flags, final counts) are
+ * for the end of the run, as before. */
+typedef struct pm_lbatch_marks pm_lbatch_marks;
+int pm_lbatch_marks_create(pm_lbatch *batch, int64_t max_chunks, pm_lbatch_marks **out);
+int pm_lbatch_marks_destroy(pm_lbatch_marks *marks);
+int pm_lbatch_run_sliced_marked(pm_lbatch *batch, const int16_t *const *h_d_audio, int recordings, int64_t n, const pm_slicer_params *h_params,
+                                int nparams, uint8_t *d_data, uint16_t *d_steps, int64_t cap, pm_rowslice_rec *d_recs, int64_t *h_nout,
+                                pm_lbatch_marks *marks, int64_t *h_chunks);
+int pm_lbatch_marks_ready(pm_lbatch_marks *marks, int64_t *h_latest);
+int pm_lbatch_marks_wait(pm_lbatch_marks *marks, int64_t t, int poll_us);
+int pm_lbatch_marks_wait_on(pm_lbatch_marks *marks, int64_t t, pm_ctx *ctx);
+int pm_lbatch_marks_view(pm_lbatch_marks *marks, int64_t t, const int64_t **d_upto, const int64_t **h_upto, const int32_t **h_flags);
 pm_ctx *pm_lbatch_front_ctx(pm_lbatch *batch);       /* the engine's own contexts, for pm_prof_*: band-pass, AGC, Hilbert of chunk t + 1 ... */
 pm_ctx *pm_lbatch_tail_ctx(pm_lbatch *batch);        /* ... and the matched filters of chunk t - 1, beside the loops of chunk t on the caller's */
 pm_ctx *pm_lbatch_loop_ctx(pm_lbatch *batch);        /* ... or on the engine's loop context, when the loops have compute units of their own (else NULL) */

@@ -373,6 +373,13 @@ _SIGS = {
     "pm_rows_carry_start": ([_vp, _vp, _i64, _int, ctypes.POINTER(RowsScanChain), _int], _int),
     "pm_rows_scan_pieces": ([_vp, _vp, _vp, _vp, _i64, _i64, _int, ctypes.POINTER(RowsScanChain), _int, _vp, _vp, ctypes.c_int32, ctypes.POINTER(_i64), _vp,
                             ctypes.c_size_t, ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_size_t)], _int),
+    "pm_lbatch_marks_create": ([_vp, _i64, ctypes.POINTER(_vp)], _int),
+    "pm_lbatch_marks_destroy": ([_vp], _int),
+    "pm_lbatch_run_sliced_marked": ([_vp, ctypes.POINTER(_vp), _int, _i64, _vp, _int, _vp, _vp, _i64, _vp, ctypes.POINTER(_i64), _vp, ctypes.POINTER(_i64)], _int),
+    "pm_lbatch_marks_ready": ([_vp, ctypes.POINTER(_i64)], _int),
+    "pm_lbatch_marks_wait": ([_vp, _i64, _int], _int),
+    "pm_lbatch_marks_wait_on": ([_vp, _i64, _vp], _int),
+    "pm_lbatch_marks_view": ([_vp, _i64, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp)], _int),
     "pm_lbatch_run": ([_vp, ctypes.POINTER(_vp), _int, _i64, _vp, _vp, _i64, ctypes.POINTER(_i64)], _int),
     "pm_lbatch_front_ctx": ([_vp], _vp),
     "pm_lbatch_tail_ctx": ([_vp], _vp),

@@ -53,6 +53,7 @@ struct pm_tuning {
     int pipe_packets = 0;              // PM_PIPE_PACKETS: pipe_scan, and the IL2P chains' attempts (headers and RS blocks) are made on the device too
     int pipe_frames = 0;               // PM_PIPE_FRAMES: pipe_scan, and the AX.25 chains' frames (de-stuffed bytes and CRC) come from the device too
     int pipe_addrs = 0;                // PM_PIPE_ADDRS: pipe_scan, and the scan jobs write address checkpoints: the host stage resolves an address where a decoder asks for one and expands none
+    int pipe_beside = 0;               // PM_PIPE_BESIDE: k >= 1: loop_batch.process_recordings_device takes the rows of a sliced engine run in pieces at every k-th mark and decodes them beside the run (implies pipe_scan); 0: behind it
     int pipe_queue_plan = 1;           // PM_PIPE_QUEUE_PLAN: where a pm_pipe makes its streams (pipe_queue_plan in pm_pipe.hip): 1 every demod stream its own, at the lowest priority level; 0 the caller's stream + one plain stream (before the plan)
     int sweep_no_tail = 0;             // PM_SWEEP_NO_TAIL: the matrix-pipe sweep sends every uncertain sample to the list (round 4), none to its own workgroup's exact chain
 };
@@ -187,6 +188,9 @@ bool pm_rowslice_made_for(const pm_rowslice *rs, const pm_slicer_params *h_param
 // samples [first, first + count) of every row (first a multiple of 64): bit k of d_bi[row * stride + k / 64] is sample first + k
 int pm_rowslice_chunk(pm_ctx *ctx, const pm_rowslice *rs, int rows, int quad, const uint64_t *d_bi, const uint64_t *d_bq, int64_t stride, int64_t first,
                       int64_t count, pm_rowslice_rec *d_recs, uint8_t *d_data, uint16_t *d_steps, int64_t cap);
+// a mark behind a chunk's slicers, on the same stream (rows_mark_kernel): min(count, cap) of every row to d_upto (device) and h_upto
+// (page-locked host), `rows` int64 each, and the OR of the rows' flags OR-ed into the device word d_flag
+int pm_rowslice_mark(pm_ctx *ctx, int rows, const pm_rowslice_rec *d_recs, int64_t cap, int64_t *d_upto, int64_t *h_upto, int32_t *d_flag);
 
 // ---- long matched filters as certified signs on the int8 matrix pipe (pm_fir8.hip): bit k of row r = (canonical FIR sum >= 0), the
 // bitmap pm_fir_rows(..., d_bits, ...) writes, for inputs of any magnitude.  A plan belongs to one tap set (m + 15 <= 1024) and device.

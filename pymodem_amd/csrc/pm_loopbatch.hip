@@ -64,6 +64,22 @@ struct pm_lbatch {
     int64_t last_chunks = 0;
 };
 
+// The marks of a sliced run (pm_lbatch_run_sliced_marked): behind the row slicers of chunk t, on their stream, every row's count as it
+// stands (rows_mark_kernel in pm_slicer.hip), the chunk's flag word, and an event.  `chunks` is what every reader goes by: the chunk count
+// of the last marked call that SUCCEEDED, 0 from the moment a marked call begins until it has recorded every one of its events -- a reader
+// can therefore never wait for an event that no call has recorded (an event nobody records never completes: a hang).
+struct pm_lbatch_marks {
+    pm_lbatch *batch = nullptr;
+    int device = 0;
+    int64_t max_chunks = 0, max_rows = 0;
+    int64_t *d_upto = nullptr, *h_upto = nullptr;            // [t * rows + row]: device / page-locked host
+    int32_t *d_flags = nullptr, *h_flags = nullptr;           // [t]
+    std::vector<hipEvent_t> ev;                               // [t], hipEventDisableTiming
+    int64_t chunks = 0, rows = 0;                             // of the last successful marked run
+    int64_t recorded = 0;                                     // events the last marked call recorded, successful or not (destroy waits for them)
+    bool loose = false;                                       // a marked call failed with launches behind its last recorded event
+};
+
 namespace {
 
 size_t put(std::vector<double> &v, const double *src, int n)
@@ -301,18 +317,142 @@ struct SliceOut {                      // pm_lbatch_run_sliced: where the rows' 
     pm_rowslice_rec *recs;
 };
 int run_impl(pm_lbatch *b, const int16_t *const *h_d_audio, int recordings, int64_t n, uint64_t *d_bits_i, uint64_t *d_bits_q, int64_t bits_stride,
-             int64_t *h_nout, const SliceOut *so);
+             int64_t *h_nout, const SliceOut *so, pm_lbatch_marks *mk);
+int run_sliced(pm_lbatch *b, const int16_t *const *h_d_audio, int recordings, int64_t n, const pm_slicer_params *h_params, int nparams, uint8_t *d_data,
+               uint16_t *d_steps, int64_t cap, pm_rowslice_rec *d_recs, int64_t *h_nout, pm_lbatch_marks *mk);
 }  // namespace
 
 int pm_lbatch_run(pm_lbatch *b, const int16_t *const *h_d_audio, int recordings, int64_t n, uint64_t *d_bits_i, uint64_t *d_bits_q,
                   int64_t bits_stride, int64_t *h_nout)
 {
     PM_ARG(b != nullptr && h_d_audio != nullptr && d_bits_i != nullptr && h_nout != nullptr);
-    return run_impl(b, h_d_audio, recordings, n, d_bits_i, d_bits_q, bits_stride, h_nout, nullptr);
+    return run_impl(b, h_d_audio, recordings, n, d_bits_i, d_bits_q, bits_stride, h_nout, nullptr, nullptr);
 }
 
 int pm_lbatch_run_sliced(pm_lbatch *b, const int16_t *const *h_d_audio, int recordings, int64_t n, const pm_slicer_params *h_params, int nparams,
                          uint8_t *d_data, uint16_t *d_steps, int64_t cap, pm_rowslice_rec *d_recs, int64_t *h_nout)
+{
+    return run_sliced(b, h_d_audio, recordings, n, h_params, nparams, d_data, d_steps, cap, d_recs, h_nout, nullptr);      // no marks: what it always enqueued
+}
+
+// ---- marks ------------------------------------------------------------------------------------------------------------------------
+int pm_lbatch_marks_destroy(pm_lbatch_marks *m)
+{
+    if (!m) return PM_OK;
+    (void)hipSetDevice(m->device);
+    // the mark launches still in flight write both copies: behind the last recorded event there is none, unless a marked call failed
+    // between a launch and its record -- then everything on the device is waited for, once
+    if (m->loose) (void)hipDeviceSynchronize();
+    else if (m->recorded > 0) (void)hipEventSynchronize(m->ev[(size_t)m->recorded - 1]);
+    for (hipEvent_t e : m->ev)
+        if (e) (void)hipEventDestroy(e);
+    if (m->d_upto) (void)hipFree(m->d_upto);
+    if (m->d_flags) (void)hipFree(m->d_flags);
+    if (m->h_upto) (void)hipHostFree(m->h_upto);
+    if (m->h_flags) (void)hipHostFree(m->h_flags);
+    delete m;
+    return PM_OK;
+}
+
+int pm_lbatch_marks_create(pm_lbatch *b, int64_t max_chunks, pm_lbatch_marks **out)
+{
+    PM_ARG(b != nullptr && out != nullptr && max_chunks >= 1 && max_chunks <= (1 << 20));
+    PM_CTX(b->back);
+    *out = nullptr;
+    pm_lbatch_marks *m = new pm_lbatch_marks();
+    m->batch = b;
+    m->device = b->back->device;
+    m->max_chunks = max_chunks;
+    m->max_rows = (int64_t)b->R * b->C;
+    const size_t cells = (size_t)m->max_chunks * (size_t)m->max_rows;
+    hipError_t e = hipMalloc((void **)&m->d_upto, cells * sizeof(int64_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&m->d_flags, (size_t)max_chunks * sizeof(int32_t));
+    if (e == hipSuccess) e = hipHostMalloc((void **)&m->h_upto, cells * sizeof(int64_t), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&m->h_flags, (size_t)max_chunks * sizeof(int32_t), hipHostMallocDefault);
+    m->ev.assign((size_t)max_chunks, nullptr);
+    for (size_t t = 0; t < m->ev.size() && e == hipSuccess; ++t) e = hipEventCreateWithFlags(&m->ev[t], hipEventDisableTiming);
+    if (e != hipSuccess) {
+        pm_lbatch_marks_destroy(m);
+        return pm_set_error(PM_ERR_HIP, "pm_lbatch_marks_create: %s", hipGetErrorString(e));
+    }
+    memset(m->h_upto, 0, cells * sizeof(int64_t));
+    memset(m->h_flags, 0, (size_t)max_chunks * sizeof(int32_t));
+    *out = m;
+    return PM_OK;
+}
+
+int pm_lbatch_run_sliced_marked(pm_lbatch *b, const int16_t *const *h_d_audio, int recordings, int64_t n, const pm_slicer_params *h_params, int nparams,
+                                uint8_t *d_data, uint16_t *d_steps, int64_t cap, pm_rowslice_rec *d_recs, int64_t *h_nout, pm_lbatch_marks *m,
+                                int64_t *h_chunks)
+{
+    PM_ARG(b != nullptr && m != nullptr && h_chunks != nullptr && m->batch == b);
+    *h_chunks = 0;
+    m->chunks = 0;                                            // from here until every event of this run is recorded the readers refuse everything
+    m->rows = 0;
+    PM_ARG(recordings >= 1 && recordings <= b->R);
+    int64_t nout = 0, chunks = 0;
+    if (int rc = pm_lbatch_geometry(b, n, &nout, nullptr, &chunks)) return rc;
+    if (chunks > m->max_chunks)
+        return pm_set_error(PM_ERR_CAPACITY, "pm_lbatch_run_sliced_marked: the run has %lld chunks, the marks were made for %lld", (long long)chunks,
+                            (long long)m->max_chunks);
+    if (int rc = run_sliced(b, h_d_audio, recordings, n, h_params, nparams, d_data, d_steps, cap, d_recs, h_nout, m)) return rc;
+    if (m->recorded != chunks || b->last_chunks != chunks) return pm_set_error(PM_ERR_ARG, "pm_lbatch_run_sliced_marked: marks and run disagree");
+    m->rows = (int64_t)recordings * b->C;
+    m->chunks = chunks;
+    *h_chunks = chunks;
+    return PM_OK;
+}
+
+#define PM_MARK_T(m, t)                                                                                                                     \
+    do {                                                                                                                                    \
+        PM_ARG((m) != nullptr);                                                                                                             \
+        if ((t) < 0 || (t) >= (m)->chunks)                                                                                                  \
+            return pm_set_error(PM_ERR_ARG, "mark %lld: the last marked run recorded marks 0 .. %lld", (long long)(t), (long long)(m)->chunks - 1); \
+    } while (0)
+
+int pm_lbatch_marks_ready(pm_lbatch_marks *m, int64_t *h_latest)
+{
+    PM_ARG(m != nullptr && h_latest != nullptr);
+    *h_latest = -1;
+    // the events complete in the order of their stream: the newest complete one by bisection, a handful of queries
+    int64_t lo = -1, hi = m->chunks;                          // lo: complete (or -1), hi: not complete (or the end)
+    while (hi - lo > 1) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        const hipError_t e = hipEventQuery(m->ev[(size_t)mid]);
+        if (e == hipSuccess) lo = mid;
+        else if (e == hipErrorNotReady) hi = mid;
+        else return pm_set_error(PM_ERR_HIP, "hipEventQuery failed: %s", hipGetErrorString(e));
+    }
+    *h_latest = lo;
+    return PM_OK;
+}
+
+int pm_lbatch_marks_wait(pm_lbatch_marks *m, int64_t t, int poll_us)
+{
+    PM_MARK_T(m, t);
+    return pm_event_sync_relaxed((void *)m->ev[(size_t)t], poll_us);
+}
+
+int pm_lbatch_marks_wait_on(pm_lbatch_marks *m, int64_t t, pm_ctx *ctx)
+{
+    PM_MARK_T(m, t);
+    PM_CTX(ctx);
+    PM_ARG(ctx->device == m->device);
+    PM_HIP(hipStreamWaitEvent(ctx->stream, m->ev[(size_t)t], 0));
+    return PM_OK;
+}
+
+int pm_lbatch_marks_view(pm_lbatch_marks *m, int64_t t, const int64_t **d_upto, const int64_t **h_upto, const int32_t **h_flags)
+{
+    PM_MARK_T(m, t);
+    if (d_upto) *d_upto = m->d_upto + t * m->rows;
+    if (h_upto) *h_upto = m->h_upto + t * m->rows;
+    if (h_flags) *h_flags = m->h_flags + t;
+    return PM_OK;
+}
+namespace {
+int run_sliced(pm_lbatch *b, const int16_t *const *h_d_audio, int recordings, int64_t n, const pm_slicer_params *h_params, int nparams, uint8_t *d_data,
+               uint16_t *d_steps, int64_t cap, pm_rowslice_rec *d_recs, int64_t *h_nout, pm_lbatch_marks *mk)
 {
     PM_ARG(b != nullptr && h_d_audio != nullptr && h_params != nullptr && d_data != nullptr && d_steps != nullptr && d_recs != nullptr && h_nout != nullptr);
     PM_ARG(nparams == b->C && cap >= 8 && cap % 8 == 0);
@@ -344,12 +484,11 @@ int pm_lbatch_run_sliced(pm_lbatch *b, const int16_t *const *h_d_audio, int reco
         b->cbits_q = (uint64_t *)qq;
     }
     const SliceOut so{d_data, d_steps, cap, d_recs};
-    return run_impl(b, h_d_audio, recordings, n, b->cbits_i, b->cbits_q, b->cstride, h_nout, &so);
+    return run_impl(b, h_d_audio, recordings, n, b->cbits_i, b->cbits_q, b->cstride, h_nout, &so, mk);
 }
 
-namespace {
 int run_impl(pm_lbatch *b, const int16_t *const *h_d_audio, int recordings, int64_t n, uint64_t *d_bits_i, uint64_t *d_bits_q, int64_t bits_stride,
-             int64_t *h_nout, const SliceOut *so)
+             int64_t *h_nout, const SliceOut *so, pm_lbatch_marks *mk)
 {
     const int tail_mode = b->back ? b->back->tune.lbatch_tail : -1;
     // The matched filters of chunk t beside the loops of chunk t + 1 (third stream; PM_LBATCH_TAIL=0: behind them on the caller's stream).
@@ -419,6 +558,11 @@ int run_impl(pm_lbatch *b, const int16_t *const *h_d_audio, int recordings, int6
     // ---- pass 2: chunk by chunk ---------------------------------------------------------------------------------------------
     const int64_t chunks = pm_cdiv(nout, Lc);
     b->last_chunks = chunks;
+    if (mk) {
+        // (pm_lbatch_run_sliced_marked has checked the marks' room; the flag words start from zero on the stream that ORs into them)
+        PM_ARG(so != nullptr && chunks <= mk->max_chunks && RC <= mk->max_rows);
+        PM_HIP(hipMemsetAsync(mk->d_flags, 0, sizeof(int32_t) * (size_t)chunks, b->slice->stream));
+    }
     int64_t s_agc = 0, s_loop = 0, prev_cnt_l = 0;
     // BPSK, one chain per recording (psk.py:168-189): the AGC's only reader is the loop -- its lane steps the follower too (pm_loops.hip)
     const bool fold_agc = pm_loops_rows_take_agc(Lp, b->modem, RC, C);
@@ -498,6 +642,16 @@ int run_impl(pm_lbatch *b, const int16_t *const *h_d_audio, int recordings, int6
                 if (int rc = pm_rowslice_chunk(Sl, b->rs, RC, b->two_out ? 1 : 0, d_bits_i + word0, b->two_out ? d_bits_q + word0 : nullptr, bits_stride, o0,
                                                o1 - o0, so->recs, so->data, so->steps, so->cap)) return rc;
                 PM_HIP(hipEventRecord(b->slice_done[t & 1], Sl->stream));
+                if (mk) {
+                    // mark t, directly behind the slicers of chunk t on their stream: the rows' counts to both copies, the chunk's flag word
+                    // to the host, then the event.  Nothing of the engine waits for any of it, least of all for the host.
+                    mk->loose = true;
+                    if (int rc = pm_rowslice_mark(Sl, RC, so->recs, so->cap, mk->d_upto + t * RC, mk->h_upto + t * RC, mk->d_flags + t)) return rc;
+                    PM_HIP(hipMemcpyAsync(mk->h_flags + t, mk->d_flags + t, sizeof(int32_t), hipMemcpyDeviceToHost, Sl->stream));
+                    PM_HIP(hipEventRecord(mk->ev[(size_t)t], Sl->stream));
+                    mk->recorded = t + 1;
+                    mk->loose = false;
+                }
             }
         }
         prev_cnt_l = cnt_l;

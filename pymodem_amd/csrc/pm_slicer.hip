@@ -700,6 +700,29 @@ __global__ __launch_bounds__(256) void rows_gather_kernel(const pm_rowslice_rec 
     for (unsigned long long i = t; i < dw; i += 256) dst[sw + i] = src_d[i];
 }
 
+// A mark of a sliced run (pm_lbatch_run_sliced_marked): behind the row slicers of a chunk, on their stream, every row's min(count, cap) as
+// an int64 into the mark's device copy and its page-locked host copy, and the OR of the rows' flags into the chunk's flag word (cleared by
+// the run's memset on the same stream).  A lane a row; the flags are OR-ed over the wave and lane 0 of the wave adds them to the word.
+// A launch of its own and NOT two more stores at the end of rowslice_kernel: that kernel is a dependent chain per lane whose register
+// count and code decide how many waves share a SIMD with the carrier loops (pm_loopbatch.hip), and an unmarked run must enqueue exactly what
+// it did -- the row slicers' build figures are the parent's (profiles/rows_beside_ab.txt).  Plain vector stores everywhere; the only
+// atomic is the wave's one OR into device memory.
+__global__ __launch_bounds__(64) void rows_mark_kernel(const pm_rowslice_rec *__restrict__ recs, int rows, int64_t cap, int64_t *__restrict__ d_upto,
+                                                       int64_t *__restrict__ h_upto, int32_t *__restrict__ d_flag)
+{
+    const int row = (int)(blockIdx.x * 64 + threadIdx.x);
+    uint32_t f = 0;
+    if (row < rows) {
+        const int64_t c = recs[row].count;
+        const int64_t v = c < cap ? c : cap;
+        d_upto[row] = v;
+        h_upto[row] = v;
+        f = (uint32_t)recs[row].flags;
+    }
+    for (int d = 32; d > 0; d >>= 1) f |= (uint32_t)__shfl_xor((int)f, d, 64);      // (every lane of the wave gets here: no row, no flags)
+    if (threadIdx.x == 0 && f) atomicOr(d_flag, (int)f);
+}
+
 // The kernels of a form, by form_index: Compare, then Hand and Event with LM0 + 2 NS0 each.
 constexpr SlicerForm kC = SlicerForm::Compare, kH = SlicerForm::Hand, kE = SlicerForm::Event;
 const char *const kFormNames[] = {"compare", "step32a", "event"};      // the [slicer] trace's name of a form
@@ -1167,6 +1190,17 @@ extern "C" int pm_rows_gather(pm_ctx *ctx, const pm_rowslice_rec *d_recs, const 
     PM_ARG(d_recs != nullptr && d_data != nullptr && d_steps != nullptr && d_block != nullptr && cap >= 8 && cap % 8 == 0 && row0 >= 0 && nrows >= 1 &&
            nrows <= 4096 && ((uintptr_t)d_block & 7) == 0);
     hipLaunchKernelGGL(rows_gather_kernel, dim3((unsigned)nrows), dim3(256), 0, ctx->stream, d_recs, d_data, d_steps, cap, row0, (uint8_t *)d_block, block_bytes);
+    PM_HIP(hipGetLastError());
+    return PM_OK;
+}
+
+// the mark behind a chunk's row slicers (rows_mark_kernel): d_upto / h_upto `rows` int64 each (device / page-locked host), d_flag one device word
+int pm_rowslice_mark(pm_ctx *ctx, int rows, const pm_rowslice_rec *d_recs, int64_t cap, int64_t *d_upto, int64_t *h_upto, int32_t *d_flag)
+{
+    PM_CTX(ctx);
+    PM_ARG(rows >= 1 && d_recs != nullptr && cap >= 8 && d_upto != nullptr && h_upto != nullptr && d_flag != nullptr);
+    PM_ARG((((uintptr_t)d_upto | (uintptr_t)h_upto) & 7) == 0);
+    hipLaunchKernelGGL(rows_mark_kernel, dim3((unsigned)pm_cdiv(rows, 64)), dim3(64), 0, ctx->stream, d_recs, rows, cap, d_upto, h_upto, d_flag);
     PM_HIP(hipGetLastError());
     return PM_OK;
 }

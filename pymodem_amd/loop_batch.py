@@ -176,11 +176,29 @@ class LoopBatch:
         if nout >= 1:
             self._sliced_room(int(recordings), nout, slicers, slot)
 
-    def run_sliced(self, audios, slicers, slot=0):
+    def _marks_for(self, slot, chunks):
+        """the slot's marks object (pm_lbatch_marks), made for at least `chunks` chunks: it lives as long as the slot's output blocks do"""
+        held = self.__dict__.setdefault("_marks", {})
+        hit = held.get(slot)
+        if hit is None or hit[1] < chunks:
+            if hit is not None:
+                check(lib().pm_lbatch_marks_destroy(hit[0]))
+                del held[slot]
+            h = ctypes.c_void_p()
+            room = max(int(chunks), 1)
+            check(lib().pm_lbatch_marks_create(self._h, room, ctypes.byref(h)))
+            hit = held[slot] = (h, room)
+        return hit[0]
+
+    def run_sliced(self, audios, slicers, slot=0, marks=False, _cap=None):
         """run() with the slicers inside the engine (pm_lbatch_run_sliced): every stream is sliced chunk by chunk behind its matched
         filter by a lane of its own, no sign bitmap of a whole recording is kept and nothing is left to slice when the run ends.
         `slicers`: one slicer object per chain -- its parameters; every stream starts from the just-tuned state (slicer.py:49-56).
-        -> SlicedRun (complete when this context's stream gets there)."""
+        -> SlicedRun (complete when this context's stream gets there).
+        marks=True (pm_lbatch_run_sliced_marked): the run also leaves, behind the slicers of every chunk, a mark -- every row's count as it
+        stands, the OR of the rows' flags and an event -- and the SlicedRun carries them (run.marks: RunMarks, run.chunks), so that its rows
+        can be taken in pieces while it runs (RowPieces.fetch(mark=t)).  The run itself is the same run.  _cap: the rows' room in bytes in
+        place of the engine's own figure (tests make a row outgrow it)."""
         r = len(audios)
         if not 1 <= r <= self.recordings:
             raise ValueError(f"LoopBatch.run_sliced: {r} recordings, the engine was made for {self.recordings}")
@@ -195,13 +213,24 @@ class LoopBatch:
             raise ValueError(f"input of {n} samples is shorter than the filters of the chain")
         params = (N.SlicerParams * self.chains)(*[sl._params() for sl in slicers])
         cap, rows, data, steps, recs = self._sliced_room(r, nout, slicers, slot)
+        if _cap is not None:
+            if not (8 <= int(_cap) <= cap and int(_cap) % 8 == 0):
+                raise ValueError("LoopBatch.run_sliced: _cap is a multiple of 8 within the rows' room")
+            cap = int(_cap)
         ptrs = (ctypes.c_void_p * r)(*[a.ptr.value for a in audios])
         got = ctypes.c_int64()
+        if marks:
+            handle, chunks = self._marks_for(slot, self.geometry(n)[2]), ctypes.c_int64()
+            check(lib().pm_lbatch_run_sliced_marked(self._h, ptrs, r, n, params, self.chains, data.ptr, steps.ptr, cap, recs.ptr, ctypes.byref(got),
+                                                    handle, ctypes.byref(chunks)))
+            return SlicedRun(self.ctx, data, steps, recs, cap, rows, got.value, marks=RunMarks(handle, rows, chunks.value), engine=self)
         check(lib().pm_lbatch_run_sliced(self._h, ptrs, r, n, params, self.chains, data.ptr, steps.ptr, cap, recs.ptr, ctypes.byref(got)))
         return SlicedRun(self.ctx, data, steps, recs, cap, rows, got.value)
 
     def close(self):
         if self._h:
+            for handle, _ in self.__dict__.pop("_marks", {}).values():
+                lib().pm_lbatch_marks_destroy(handle)        # (in front of the engine: waits for the marks still in flight)
             lib().pm_lbatch_destroy(self._h)                 # waits for both of the engine's streams
             self._h = ctypes.c_void_p()
             pool = self.ctx.__dict__.get("_pool", {})
@@ -216,12 +245,76 @@ class LoopBatch:
             pass
 
 
+def next_mark(last, newest, chunks, k):
+    """Which mark the driver of process_recordings_device(beside=k) takes next, or None: `last` the mark it took last (-1: none yet), `newest`
+    the newest mark whose event has completed (pm_lbatch_marks_ready; -1: none), `chunks` the run's chunk count.  Due are the marks t with
+    (t + 1) % k == 0; they are taken in order, each at most once; once the run's LAST mark has completed nothing more is due -- the rows are
+    all there and go in one final piece."""
+    if chunks < 1 or newest >= chunks - 1:
+        return None
+    t = (last + 1 + k) // k * k - 1                          # the first t > last with (t + 1) % k == 0
+    return t if t < chunks else None
+
+
+def piece_cut(avail, taken, final=False):
+    """pm_rows_scan_pieces' rule for the next piece of rows that have `avail` bytes to give (min(upto, count, cap)) and have given `taken`:
+    n = avail - taken, rounded down to a multiple of 8 unless final, never below 0; nothing behind a final piece (taken % 8 != 0)"""
+    taken = np.asarray(taken, dtype=np.int64)
+    n = np.asarray(avail, dtype=np.int64) - taken
+    if not final:
+        n = n // 8 * 8                                       # (floor: rounds down below zero too)
+    return np.ascontiguousarray(np.where(taken % 8 != 0, 0, np.maximum(n, 0)), dtype=np.int64)
+
+
+class RunMarks:
+    """The marks of one marked run (pm_lbatch_marks_*; the engine owns the object): chunks marks of `rows` int64 each.  Every reader refuses
+    a t outside [0, chunks) -- so does the library -- and none of them touches the run's records."""
+
+    def __init__(self, handle, rows, chunks):
+        self._h, self.rows, self.chunks = handle, int(rows), int(chunks)
+
+    def ready(self):
+        """the newest mark whose event has completed, -1 if none: no waiting"""
+        t = ctypes.c_int64()
+        check(lib().pm_lbatch_marks_ready(self._h, ctypes.byref(t)))
+        return t.value
+
+    def wait(self, t, poll_us=200):
+        """host wait for mark t without spinning; its host copies may be read afterwards"""
+        check(lib().pm_lbatch_marks_wait(self._h, int(t), int(poll_us)))
+
+    def wait_on(self, t, ctx):
+        """what is submitted to ctx from now on waits, on the GPU, for mark t"""
+        check(lib().pm_lbatch_marks_wait_on(self._h, int(t), ctx.handle))
+
+    def _view(self, t):
+        d, h, f = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        check(lib().pm_lbatch_marks_view(self._h, int(t), ctypes.byref(d), ctypes.byref(h), ctypes.byref(f)))
+        return d.value, h.value, f.value
+
+    def d_upto(self, t, row0=0):
+        """device address of mark t's int64 of row row0"""
+        return self._view(t)[0] + 8 * int(row0)
+
+    def h_upto(self, t):
+        """mark t's `rows` int64 in page-locked host memory, as an array over that memory (read it behind wait(t))"""
+        at = self._view(t)[1]
+        return np.ctypeslib.as_array((ctypes.c_int64 * self.rows).from_address(at))
+
+    def flags(self, t):
+        """the OR of the rows' flags at mark t (read it behind wait(t))"""
+        return int(ctypes.c_int32.from_address(self._view(t)[2]).value)
+
+
 class SlicedRun:
     """What a sliced engine run left in device memory: per stream (row = recording * chains + chain) its data bytes, address steps and
-    record.  records() and fetch() want the run complete (synchronise the context it ran on first)."""
+    record.  records() and fetch() want the run complete (synchronise the context it ran on first).  A run made with marks=True carries them
+    (marks: RunMarks, chunks): RowPieces.fetch(mark=t) takes its rows while it runs."""
 
-    def __init__(self, ctx, data, steps, recs, cap, rows, nout):
+    def __init__(self, ctx, data, steps, recs, cap, rows, nout, marks=None, engine=None):
         self.ctx, self.data, self.steps, self.recs, self.cap, self.rows, self.nout = ctx, data, steps, recs, cap, rows, nout
+        self.marks, self.chunks = marks, (marks.chunks if marks is not None else None)
+        self._engine = engine                                # (the marks are the engine's: it lives as long as they are read)
         self._records = None
         self.copied = 0                                      # bytes that fetch() and fetch_scanned() have brought to the host (diagnosis)
         self._copied_lock = threading.Lock()
@@ -336,39 +429,54 @@ class RowPieces:
         self.taken = np.zeros(run.rows, dtype=np.int64)      # the host's shadow of pm_rows_carry.taken
         self.begun = np.zeros(run.rows, dtype=bool)
         self.last_from = np.zeros(run.rows, dtype=np.int64)  # where each row's last piece began
+        self.last_before = np.zeros(run.rows, dtype=np.int64)    # its addr_before
+        self.at_mark = np.zeros(run.rows, dtype=bool)        # and whether it was taken at a mark (raw() then copies it directly)
         self.seeds = self.ordinary = 0
         self._lock = threading.Lock()
 
-    def piece_bytes(self, row0, nrows, upto=None, final=False):
-        """n of the next piece of every row, by pm_rows_scan_pieces' rule, from the records and the shadow of `taken`"""
-        recs = self.run.records()[row0:row0 + nrows]
+    def piece_bytes(self, row0, nrows, upto=None, final=False, mark=None):
+        """n of the next piece of every row, by pm_rows_scan_pieces' rule, from the records and the shadow of `taken` -- or, with `mark`, from
+        the mark's host copy alone (min(count, cap) as it stood at the mark: wait for the mark first), with no look at the records: the run
+        may still be going, and records() would cache what it found for good"""
         taken = self.taken[row0:row0 + nrows]
+        if mark is not None:
+            assert upto is None, "a piece at a mark goes up to the mark"
+            return piece_cut(np.minimum(self.run.marks.h_upto(mark)[row0:row0 + nrows], self.run.cap), taken, final)
+        recs = self.run.records()[row0:row0 + nrows]
         avail = np.clip(recs["count"], 0, self.run.cap)
         if upto is not None:
             avail = np.minimum(avail, np.asarray(upto, dtype=np.int64))
-        n = avail - taken
-        if not final:
-            n = n // 8 * 8                                   # (floor: rounds down below zero too)
-        return np.ascontiguousarray(np.where(taken % 8 != 0, 0, np.maximum(n, 0)), dtype=np.int64)
+        return piece_cut(avail, taken, final)
 
-    def fetch(self, row0, nrows, upto=None, final=False, copy_ctx=None, tag=None):
+    def fetch(self, row0, nrows, upto=None, final=False, copy_ctx=None, tag=None, mark=None):
         """The next piece of rows row0 .. row0 + nrows - 1: up to `upto` bytes of each row (an int64 per row, None: the records' counts), cut at
         a multiple of 8 unless `final`.  -> per row (the piece's address steps, addr_before, n, the piece's scan part with its carry piece) as
-        views of one host block: the upload of `upto`, one pm_rows_scan_pieces and ONE copy to the host for the lot."""
+        views of one host block: the upload of `upto`, one pm_rows_scan_pieces and ONE copy to the host for the lot.
+        mark=t (a run made with marks=True, which may still be going): up to what every row had when mark t was made.  The fetching context
+        waits for the mark on the GPU, `upto` is the mark's own device copy -- nothing is uploaded -- and the sizes come from its host copy, read
+        behind a relaxed host wait; the run's records are not touched."""
         run = self.run
         ctx = copy_ctx or run.ctx
         nchains = len(self.chains)
+        if mark is not None:
+            if run.marks is None or upto is not None:
+                raise ValueError("RowPieces.fetch: mark= wants a run made with marks=True and no upto")
+            run.marks.wait_on(mark, ctx)                     # in front of everything this call enqueues, the carries' start included
+            run.marks.wait(mark)
         if not self.begun[row0:row0 + nrows].all():
             check(lib().pm_rows_carry_start(ctx.handle, self.carries.ptr, row0, nrows, self.desc, nchains))
             self.begun[row0:row0 + nrows] = True
-        counts = self.piece_bytes(row0, nrows, upto, final)
+        counts = self.piece_bytes(row0, nrows, upto, final, mark)
         key = tag if tag is not None else ("sliced-run", id(run))
         d_upto = None
-        if upto is not None:
+        if mark is not None:
+            d_upto = ctypes.c_void_p(run.marks.d_upto(mark, row0))
+        elif upto is not None:
             h_upto = np.ascontiguousarray(upto, dtype=np.int64)
             assert len(h_upto) == nrows
-            d_upto = ctx.scratch((key, "upto"), nrows, np.int64)
-            check(lib().pm_h2d(ctx.handle, d_upto.ptr, h_upto.ctypes.data_as(ctypes.c_void_p), h_upto.nbytes))
+            buf = ctx.scratch((key, "upto"), nrows, np.int64)
+            check(lib().pm_h2d(ctx.handle, buf.ptr, h_upto.ctypes.data_as(ctypes.c_void_p), h_upto.nbytes))
+            d_upto = buf.ptr
         of = [self.desc[(row0 + k) % nchains] for k in range(nrows)]
         sizes = [N.rows_piece_part_bytes(d.codec_kind, d.frames, d.packets, int(c), d.addrs) for d, c in zip(of, counts)]
         used = int(sum(sizes))
@@ -377,7 +485,7 @@ class RowPieces:
         block = ctx.scratch((key, "pieces"), room, np.uint8)
         offs, need = (ctypes.c_int64 * nrows)(), ctypes.c_size_t()
         check(lib().pm_rows_scan_pieces(ctx.handle, run.recs.ptr, run.data.ptr, run.steps.ptr, run.cap, row0, nrows, self.desc, nchains, self.carries.ptr,
-                                        d_upto.ptr if d_upto is not None else None, int(bool(final)), counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                        d_upto, int(bool(final)), counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
                                         block.ptr, block.n, offs, ctypes.byref(need)))
         assert need.value == used, "pm_rows_scan_pieces and _native.rows_piece_part_bytes size a piece alike"
         host = block.download(used, recycle=True, ctx=ctx, room=room)
@@ -385,18 +493,31 @@ class RowPieces:
             run.copied += used
         self.last_from[row0:row0 + nrows] = self.taken[row0:row0 + nrows]
         self.taken[row0:row0 + nrows] += counts
+        self.at_mark[row0:row0 + nrows] = mark is not None
         out = []
         for k in range(nrows):
             c, o = int(counts[k]), int(offs[k])
             sw, end = N.rows_scan_steps_bytes(c), o + sizes[k]
-            out.append((host[o:o + 2 * c].view(np.uint16), int(host[end - 8:end].view(np.int64)[0]), c, host[o + sw:end - 8]))
+            before = int(host[end - 8:end].view(np.int64)[0])
+            self.last_before[row0 + k] = before
+            out.append((host[o:o + 2 * c].view(np.uint16), before, c, host[o + sw:end - 8]))
         return out
 
     def raw(self, row, copy_ctx=None, tag=None):
-        """the slicer bytes of the row's last piece, for a piece that goes the ordinary way (SlicedRun.fetch brings the row)"""
+        """the slicer bytes of the row's last piece, for a piece that goes the ordinary way (SlicedRun.fetch brings the row).  A piece that was
+        taken at a mark is copied directly -- bytes [last_from, taken) of the row and their steps, the addresses from the piece's addr_before,
+        whose first step counts: the run may still be going, and SlicedRun.fetch (records, pm_rows_gather over the moving counts) is for a
+        run that is complete.  On the context that fetched the piece: it has waited for the mark."""
         from .data_classes import AddressedArray
-        whole = self.run.fetch(row, 1, copy_ctx, tag)[0]
         a, b = int(self.last_from[row]), int(self.taken[row])
+        if self.at_mark[row]:
+            run, ctx = self.run, copy_ctx or self.run.ctx
+            if b <= a:
+                return AddressedArray(np.zeros(0, np.uint8), np.zeros(0, np.int64))
+            data = run.data.view(row * run.cap + a, b - a).download(ctx=ctx)
+            steps = run.steps.view(row * run.cap + a, b - a).download(ctx=ctx)
+            return AddressedArray(np.ascontiguousarray(data), int(self.last_before[row]) + np.cumsum(steps.astype(np.int64)))
+        whole = self.run.fetch(row, 1, copy_ctx, tag)[0]
         return AddressedArray(np.ascontiguousarray(whole.data[a:b]), np.ascontiguousarray(whole.address[a:b]))
 
     def seed(self, row, lfsr_state, ones, counted, copy_ctx=None):
@@ -451,8 +572,131 @@ def _scannable(chain_sets):
     return len(chain_sets[0]) <= 64 and all(what(ch) == what(first) for cs in chain_sets for ch, first in zip(cs, chain_sets[0]))
 
 
+def _fetch_groups(ctx, r, nchains):
+    """how a run's rows go to the host: -> (parts, recordings per fetch, the parts' cuts, their side contexts)"""
+    import os
+    parts = max(1, min(int(os.environ.get("PYMODEM_AMD_LOOP_SLICE_STREAMS", "8")), r))
+    per = max(1, int(os.environ.get("PYMODEM_AMD_LOOP_FETCH_ROWS", "256")) // nchains)
+    return parts, per, [r * p // parts for p in range(parts + 1)], [Context.side(ctx.device, 400 + p) for p in range(parts)]
+
+
+def _beside(eng, chain_sets, dev, ctx, k, rows, chain_ids, stages, slot, frames, packets, addrs, t0):
+    """process_recordings_device's route with beside=k: the marked run, and this thread driving its marks where it would sleep through the run.
+    -> the function that does the remainder and returns the result, or {"gave_up": t} with the run complete and the chains as they were
+    at entry.  Nothing here looks at the run's records before the run is complete."""
+    import time
+    from .chain_execute import _host_rows_pieces, _pool
+    from ._native import quick
+    from .packet_meta import rows_to_packets
+    r, nchains = len(chain_sets), len(chain_sets[0])
+    registers = [[ch[3].shift_register for ch in cs] for cs in chain_sets]
+    run = eng.run_sliced(dev, [ch[2] for ch in chain_sets[0]], slot=(slot, 0), marks=True)
+    marks, chunks = run.marks, run.chunks
+    parts, per, cuts, _ = _fetch_groups(ctx, r, nchains)
+    # Side contexts and block tags of this slot's own, not the 400 + p of the remainders: with defer=True the remainder of the run before
+    # this one (its final pieces, on another thread) lies beside this run's pieces at the marks, and a context's scan scratch and its
+    # fetch block serve one call at a time.  A run's pieces, the final one included, all go through the same context.
+    lane = 16 * (slot % 2) if isinstance(slot, int) else 0
+    sides = [Context.side(ctx.device, 420 + lane + p) for p in range(parts)]
+    tags = [("loop-beside", lane, p) for p in range(parts)]
+    got_rows = [[[] for _ in range(nchains)] for _ in range(r)]
+    state = {"taker": None, "early_bytes": 0}
+    lock = threading.Lock()
+
+    def take(p, t):
+        # the next piece of this part's rows -- at mark t, or (None) the final one -- a group at a time: every piece is decoded, and the
+        # carries that it names are seeded again, before the next piece of the same rows is fetched
+        taker, n = state["taker"], 0
+        for lo in range(cuts[p], cuts[p + 1], per):
+            hi = min(lo + per, cuts[p + 1])
+            row0, nr = lo * nchains, (hi - lo) * nchains
+            got = taker.fetch(row0, nr, None, t is None, sides[p], tag=tags[p], mark=t)
+            n += sum(g[2] for g in got)
+            for rec in range(lo, hi):
+                views, again, ordinary = _host_rows_pieces(chain_sets[rec], got[(rec - lo) * nchains:(rec - lo + 1) * nchains], chain_ids, frames, packets,
+                                                           addrs, lambda j, rec=rec: taker.raw(rec * nchains + j, sides[p], tags[p]))
+                for c, v in enumerate(views):
+                    got_rows[rec][c].append(v)
+                taker.went_ordinary(ordinary)
+                for j, reg, ones, counted in again:
+                    taker.seed(rec * nchains + j, reg, ones, counted, sides[p])
+        if t is not None:
+            with lock:
+                state["early_bytes"] += n
+
+    def take_all(t):
+        if state["taker"] is None:
+            state["taker"] = run.pieces(chain_sets[0], frames, packets, addrs)
+        for f in [_pool().submit(take, p, t) for p in range(parts)]:
+            f.result()
+
+    def give_up(t):
+        ctx.sync_relaxed()                                   # the run goes to its end: its engine and its blocks are the next run's
+        for cs, regs in zip(chain_sets, registers):
+            for ch, reg in zip(cs, regs):
+                ch[3].shift_register = reg
+                if ch[4]._h is not None:                     # never fed again: the pieces' decoder goes, the next use makes a new one
+                    quick().pm_codec_destroy(ch[4]._h)
+                    ch[4]._h = None
+        return {"gave_up": int(t)}
+
+    taken, last = [], -1
+    while True:
+        t = next_mark(last, marks.ready(), chunks, k)
+        if t is None:
+            break
+        marks.wait(t)
+        if marks.flags(t):
+            return give_up(t)
+        take_all(t)
+        taken.append(t)
+        last = t
+    ctx.sync_relaxed()
+    t1 = time.perf_counter()
+    run.records(Context.side(ctx.device, 399))              # (now, and not before: the run is complete)
+    if not run.ok():
+        # (the run got to its end before the driver got to the mark that says so: every mark is there to be read now -- the first due one
+        # with a flag, as if the driver had been in time, or the run's last mark where none was due any more)
+        return give_up(next((t for t in range(last + 1, chunks) if (t + 1) % k == 0 and marks.flags(t)), chunks - 1))
+
+    def rest():
+        for rec in range(r):
+            for c in range(nchains):
+                sl = chain_sets[rec][c][2]
+                sl._ctx = sl._ctx or ctx
+                run.state_into(rec * nchains + c, sl)
+        take_all(None)
+        sliced = []
+        if stages is not None:                               # (diagnosis only: the slicers' bytes as the old way brings them)
+            for p in range(parts):
+                for lo in range(cuts[p], cuts[p + 1], per):
+                    sliced += run.fetch(lo * nchains, (min(lo + per, cuts[p + 1]) - lo) * nchains, sides[p], tag=tags[p])
+        t2 = time.perf_counter()
+
+        def joined(rec):
+            # (packet rows are 1.3 KB each, gigabytes a run: a chain whose packets all came in one piece keeps that block, the others are
+            # copied on the library's threads, a recording each -- new pages are touched faster by many)
+            blocks = []
+            for v in got_rows[rec]:
+                some = [x for x in v if len(x)]
+                blocks.append(some[0] if len(some) == 1 else np.concatenate(v))
+            return blocks if rows else [rows_to_packets(b, ch[4].identifier) for ch, b in zip(chain_sets[rec], blocks)]
+        out = list(_pool().map(joined, range(r)))
+        if stages is not None:
+            taker = state["taker"]
+            stages["sliced"] = [sliced[rec * nchains:(rec + 1) * nchains] for rec in range(r)]
+            stages["seconds"] = {"engine": t1 - t0, "slicers": t2 - t1, "host": time.perf_counter() - t2}
+            stages["fused_slicers"] = True
+            stages["scanned"] = True
+            stages["copied_bytes"] = run.copied
+            stages["beside"] = {"every": k, "chunks": chunks, "marks": taken, "seeds": taker.seeds, "ordinary": taker.ordinary,
+                                "bytes_before_end": state["early_bytes"]}
+        return out
+    return rest
+
+
 def process_recordings_device(chain_sets, audios, ctx=None, chunk=0, rows=False, chain_ids=None, stages=None, slot=0, defer=False, scan=None,
-                              frames=None, packets=None, addrs=None, pieces=None):
+                              frames=None, packets=None, addrs=None, pieces=None, beside=None):
     """chain_sets[k] = the chains [name, modem, slicer, stream, codec] of recording k (every recording brings the same group of
     chains, as a service decoding successive recordings with one config does), audios[k] its int16 samples (host array or
     DeviceBuffer; equal lengths).  -> [[packets of chain 0, ...] per recording], identical to chain_execute.process_chain on each
@@ -470,7 +714,17 @@ def process_recordings_device(chain_sets, audios, ctx=None, chunk=0, rows=False,
     then False): every group of rows is taken in k pieces through RowPieces -- up to count * p // k bytes of each row for p = 1 .. k - 1, then
     the final piece -- and each piece is decoded by the carried host route before the next piece of the same rows is fetched, as an engine
     that hands over its rows per time chunk would drive it.  Results are the same, nothing is faster; stages["pieces"] = {"pieces": k,
-    "seeds": carries seeded again behind a bail, "ordinary": pieces that went the ordinary way}."""
+    "seeds": carries seeded again behind a bail, "ordinary": pieces that went the ordinary way}.
+    beside (None: the context's switch pipe_beside, PM_PIPE_BESIDE, default 0; 0: off, nothing changes; an integer k >= 1; anything else
+    raises; implies scan; not together with pieces): the host decodes BESIDE the engine's run instead of behind it.  The run is made with
+    marks (LoopBatch.run_sliced(marks=True)) and this thread, where it would sleep through the run, takes the rows in pieces at the marks t
+    with (t + 1) % k == 0 as they complete (next_mark): per group of rows RowPieces.fetch(mark=t), then the carried host route, every row's
+    piece decoded before its next one is fetched.  What is left when the run ends -- the records, the slicers' end states, one final piece --
+    is the remainder (with defer=True the caller's, as ever).  A mark whose flag word is set, or a run that is not ok() at its end, means
+    the run is to be redone from sign bitmaps: the chains' LFSR registers go back to what they were, the native codecs that the pieces fed
+    are dropped (never fed, as at entry), the rows gathered are discarded, stages["beside"] = {"gave_up": t}.  Ignored where pieces is
+    ignored (stages["beside"] = False).  Results are the same; stages["beside"] = {"every": k, "chunks": the run's, "marks": [those taken],
+    "seeds", "ordinary", "bytes_before_end": slicer bytes decoded from pieces in front of the final one}."""
     from .chain_execute import _host_rows, _host_rows_pieces, _host_rows_scanned, _host_stages, _host_stages_scanned, _pool
     from .slicer import slice_batch
     ctx = ctx or Context.default()
@@ -483,6 +737,15 @@ def process_recordings_device(chain_sets, audios, ctx=None, chunk=0, rows=False,
     scan = (bool(ctx.tuned("pipe_scan")) if scan is None else bool(scan)) or frames or packets or addrs
     if pieces is not None and (int(pieces) != pieces or pieces < 2):
         raise ValueError("process_recordings_device: pieces is an integer >= 2")
+    if beside is None:
+        beside = ctx.tuned("pipe_beside")
+    if isinstance(beside, bool) or not isinstance(beside, (int, np.integer)) or beside < 0:
+        raise ValueError("process_recordings_device: beside is 0 or an integer >= 1 (pipe_beside / PM_PIPE_BESIDE likewise)")
+    beside = int(beside)
+    if beside and pieces is not None:
+        raise ValueError("process_recordings_device: beside and pieces are two ways to cut the same rows; one of them")
+    scan = scan or bool(beside)
+    gave_up = None
     dev = []
     for a in audios:
         if isinstance(a, DeviceBuffer):
@@ -515,11 +778,17 @@ def process_recordings_device(chain_sets, audios, ctx=None, chunk=0, rows=False,
             and all(hasattr(ch[2], "_params_bytes") and bytes(ch[2]._state) == fresh for cs in chain_sets for ch in cs)
             and all(cs[c][2]._params_bytes() == chain_sets[0][c][2]._params_bytes() for cs in chain_sets for c in range(nchains))):
         eng = engine_for([ch[1] for ch in chain_sets[0]], r, ctx, chunk)
-        run = eng.run_sliced(dev, [ch[2] for ch in chain_sets[0]], slot=(slot, 0))
-        ctx.sync_relaxed()
-        t1 = time.perf_counter()
-        run.records(Context.side(ctx.device, 399))          # (not on the context's own stream: the next run may be queued on it by now)
-        if run.ok():
+        if beside and _scannable(chain_sets):
+            done = _beside(eng, chain_sets, dev, ctx, beside, rows, chain_ids, stages, slot, frames, packets, addrs, t0)
+            if not isinstance(done, dict):
+                return done if defer else done()
+            gave_up = done                                   # (the run is complete and everything the pieces moved is back where it was)
+        run = None if gave_up else eng.run_sliced(dev, [ch[2] for ch in chain_sets[0]], slot=(slot, 0))
+        if run is not None:
+            ctx.sync_relaxed()
+            t1 = time.perf_counter()
+            run.records(Context.side(ctx.device, 399))      # (not on the context's own stream: the next run may be queued on it by now)
+        if run is not None and run.ok():
             scanned = scan and _scannable(chain_sets)       # (foreign stream or codec objects, or codecs that have been used, go the old way)
             in_pieces = int(pieces) if scanned and pieces is not None else 0
 
@@ -600,6 +869,8 @@ def process_recordings_device(chain_sets, audios, ctx=None, chunk=0, rows=False,
                     stages["copied_bytes"] = run.copied     # (with the scan on: the plain fetch for stages["sliced"] counted too)
                     if pieces is not None:
                         stages["pieces"] = {"pieces": in_pieces, "seeds": taker.seeds, "ordinary": taker.ordinary} if in_pieces else False
+                    if beside:
+                        stages["beside"] = False                 # (chains that the row form of the scan cannot describe: ignored)
                 if scanned:
                     out = [early[rec].result() for rec in range(r)]
                     if stages is not None:
@@ -670,6 +941,8 @@ def process_recordings_device(chain_sets, audios, ctx=None, chunk=0, rows=False,
         stages["seconds"] = {"engine": t1 - t0, "slicers": t2 - t1}
         if pieces is not None:
             stages["pieces"] = False                         # (not the fused-slicer route: ignored)
+        if beside:
+            stages["beside"] = gave_up if gave_up else False
     out = []
     if rows:
         futs = [early[rec] if rec in early else _pool().submit(_host_rows, chain_sets[rec], sliced[rec * nchains:(rec + 1) * nchains], chain_ids)
