@@ -660,7 +660,67 @@ int pm_rows_carry_start(pm_ctx *ctx, pm_rows_carry *d_carries, int64_t row0, int
 int pm_rows_scan_pieces(pm_ctx *ctx, const pm_rowslice_rec *d_recs, const uint8_t *d_data, const uint16_t *d_steps, int64_t cap, int64_t row0, int nrows,
                         const pm_rows_scan_chain *h_chains, int nchains, pm_rows_carry *d_carries, const int64_t *d_upto, int32_t final,
                         const int64_t *h_counts, void *d_block, size_t block_bytes, int64_t *h_offsets, size_t *h_used);
-/* MARKS: a sliced run that says, chunk by chunk, how far every row has got -- what pm_rows_scan_pieces' d_upto is shaped for, so that the
+/* FINISHED ROWS: the pm_packet rows of rows [row0, row0 + nrows) of a sliced run, made on the device from the block that pm_rows_scan has
+ * just written for the same rows -- exactly the rows that pm_codec_fetch hands out for a just-created codec that is fed the row
+ * (pm_codec_decode_addrs), wherever the row's frame table or packet table says everything about it.  Enqueued on the ctx stream behind that
+ * pm_rows_scan; d_recs, d_steps, cap, row0, nrows, h_chains, nchains, h_counts, d_block and h_offsets are its arguments and results, unchanged.
+ * Every chain with a codec must have been scanned with the table of its kind (frames for AX.25, packets for IL2P) and with addrs;
+ * PM_ERR_ARG otherwise.  (A chain of kind -1 has no packets: its rows are entered as NO_CODEC.)  h_sources[c]: what goes into
+ * pm_packet.source_decoder for chain c, NULL: c.
+ * d_block must be DEVICE memory: these launches read it -- the record, the list, the descrambled bytes, the table, the area and the
+ * checkpoints of every row.  If the runtime says it is host memory the call returns PM_ERR_ARG.  (pm_rows_scan's own launches never read
+ * the block: what they need of their own results they keep in context scratch, which is why its block may be page-locked host memory.)
+ * d_out (8-byte aligned, out_bytes of device memory) receives
+ *     pm_rows_packets_head                 16 bytes: the rows of the call, how many of them are not FINISHED, the packet rows that follow
+ *     pm_rows_packets_entry[nrows]         32 bytes a row
+ *     pm_packet[head.packets]              in row order; a row's packets lie at `first`, consecutively, in stream order
+ * so that the rows of a recording lie chain after chain in config order.  An entry holds the LFSR register behind the row (the scan
+ * record's), a status, the row's packet count, its first packet row, and for a FINISHED IL2P row the decoder's count of corrected bytes
+ * that no packet has taken (il2p.py:203-212 never clears it when a block fails).  Status FINISHED: the packets are all there is to say about
+ * the row.  Every other status names why the row is handed over -- it has no packet rows and is decoded the existing way:
+ *     IL2P   NO_RECORD   the decoder's sync test hits where the table has no record (a place its register finds and the bitmap does not)
+ *            INCOMPLETE / NOT_PLACED   the record at a hit is one
+ *            LATE_HIT    a second hit in the byte in which an attempt ends
+ *            TABLE_FULL  the table has no free place left: candidates may have gone without a record
+ *     AX.25  SHORT       fewer than 24 bytes (pm_codec_decode_framed walks such a stream)
+ *            BAIL        the record has a bail bit: frames may lie behind it
+ *            LONG_FRAME  a table entry with more bytes than the span between its flags holds (pm_codec_decode_framed refuses such a table).
+ *                        A frame longer than PM_PKT_MAX is no reason: its row is cut as pm_codec_fetch cuts it.
+ *     any    LEFT_OUT    pm_rows_scan left the row out (records and h_counts disagree)
+ *            NO_ROOM     see below
+ *            NO_CODEC    the row's chain has codec_kind -1
+ * The packet capacity is what out_bytes leaves behind the entries, in whole rows.  The first row whose packets would pass it takes none and
+ * is NO_ROOM, and so is every row behind it, whatever its walk said; their `first` is head.packets.  *h_used = the smallest out_bytes that
+ * holds head and entries (PM_ERR_CAPACITY, with it set, when out_bytes is less).  Nothing is uploaded, allocated beyond context scratch or
+ * waited for.  nrows <= 4096, nchains <= 64.  Three launches: a lane a row walks the row's table by the rule (pm_rows_packets.h) and lists
+ * what it accepts in context scratch; one workgroup scans the rows' counts, trips of 256 with a carry, for `first`, NO_ROOM and the head;
+ * a fixed grid of waves builds the packet rows, wave w the packets w, w + waves, ... */
+#define PM_ROWS_PACKETS_FINISHED 0
+#define PM_ROWS_PACKETS_NO_RECORD 1
+#define PM_ROWS_PACKETS_INCOMPLETE 2
+#define PM_ROWS_PACKETS_NOT_PLACED 3
+#define PM_ROWS_PACKETS_LATE_HIT 4
+#define PM_ROWS_PACKETS_TABLE_FULL 5
+#define PM_ROWS_PACKETS_SHORT 6
+#define PM_ROWS_PACKETS_BAIL 7
+#define PM_ROWS_PACKETS_LONG_FRAME 8
+#define PM_ROWS_PACKETS_LEFT_OUT 9
+#define PM_ROWS_PACKETS_NO_ROOM 10
+#define PM_ROWS_PACKETS_NO_CODEC 11
+typedef struct pm_rows_packets_head {
+    int32_t rows, handed;
+    int64_t packets;
+} pm_rows_packets_head;
+typedef struct pm_rows_packets_entry {
+    uint64_t lfsr_state;
+    int32_t status, packets;
+    int64_t first;
+    int32_t corrected_left, reserved;
+} pm_rows_packets_entry;
+int pm_rows_packets(pm_ctx *ctx, const pm_rowslice_rec *d_recs, const uint16_t *d_steps, int64_t cap, int64_t row0, int nrows,
+                    const pm_rows_scan_chain *h_chains, int nchains, const int32_t *h_sources, const int64_t *h_counts, const void *d_block,
+                    const int64_t *h_offsets, void *d_out, size_t out_bytes, size_t *h_used);
+/* MARKS:a sliced run that says, chunk by chunk, how far every row has got -- what pm_rows_scan_pieces' d_upto is shaped for, so that the
  * rows of a run can be taken and decoded BESIDE the run instead of behind it.  A pm_lbatch_marks object (made for one engine and up to
  * max_chunks chunks; destroy it before the engine) holds for each chunk t of a run:
  *   - an int64 per row in device memory (8-byte aligned, mark t's row r at index t * rows + r, rows = recordings * chains of that run):

@@ -198,6 +198,28 @@ def rows_piece_part_bytes(kind, frames, packets, n, addrs=0):
     return rows_scan_steps_bytes(n) + scan_part_bytes(kind, frames, packets, n, addrs) + ROWS_PIECE_TAIL_BYTES
 
 
+# pm_rows_packets: PM_ROWS_PACKETS_*, an entry's status in this order
+ROWS_PACKETS_STATUS = ("FINISHED", "NO_RECORD", "INCOMPLETE", "NOT_PLACED", "LATE_HIT", "TABLE_FULL", "SHORT", "BAIL", "LONG_FRAME", "LEFT_OUT", "NO_ROOM", "NO_CODEC")
+ROWS_PACKETS_HEAD_BYTES, ROWS_PACKETS_ENTRY_BYTES = 16, 32
+
+
+def rows_packets_head_dtype():
+    """NumPy view of pm_rows_packets_head: what pm_rows_packets' d_out begins with."""
+    import numpy as np
+    return np.dtype([("rows", "<i4"), ("handed", "<i4"), ("packets", "<i8")])
+
+
+def rows_packets_entry_dtype():
+    """NumPy view of pm_rows_packets_entry: a row of pm_rows_packets' d_out."""
+    import numpy as np
+    return np.dtype([("lfsr_state", "<u8"), ("status", "<i4"), ("packets", "<i4"), ("first", "<i8"), ("corrected_left", "<i4"), ("reserved", "<i4")])
+
+
+def rows_packets_bytes(nrows, packets=0):
+    """out_bytes of pm_rows_packets for nrows rows and room for `packets` packet rows."""
+    return ROWS_PACKETS_HEAD_BYTES + ROWS_PACKETS_ENTRY_BYTES * nrows + ctypes.sizeof(Packet) * packets
+
+
 def scan_packet_dtype():
     """NumPy view of a place of the packet table."""
     import numpy as np
@@ -370,6 +392,8 @@ _SIGS = {
     "pm_rows_gather": ([_vp, _vp, _vp, _vp, _i64, _i64, _int, _vp, ctypes.c_size_t], _int),
     "pm_rows_scan": ([_vp, _vp, _vp, _vp, _i64, _i64, _int, ctypes.POINTER(RowsScanChain), _int, ctypes.POINTER(_i64), _vp, ctypes.c_size_t,
                      ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_size_t)], _int),
+    "pm_rows_packets": ([_vp, _vp, _vp, _i64, _i64, _int, ctypes.POINTER(RowsScanChain), _int, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_i64), _vp,
+                         ctypes.POINTER(_i64), _vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)], _int),
     "pm_rows_carry_start": ([_vp, _vp, _i64, _int, ctypes.POINTER(RowsScanChain), _int], _int),
     "pm_rows_scan_pieces": ([_vp, _vp, _vp, _vp, _i64, _i64, _int, ctypes.POINTER(RowsScanChain), _int, _vp, _vp, ctypes.c_int32, ctypes.POINTER(_i64), _vp,
                             ctypes.c_size_t, ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_size_t)], _int),

@@ -30,12 +30,16 @@
 // pm_rows_scan_pieces is the row form with such a carry per row (pm_rows_carry): a third source, RowPieceJobs, whose table entries say where in
 // its row a piece begins and which address lies in front of it; the prepare launch cuts the pieces from the carries' `taken`, and the combine
 // launch's lane 0 moves `taken` and `last_addr` on beside the carry-out.
+// pm_rows_packets, behind pm_rows_scan on the same stream, READS a block in device memory: a lane a row walks the row's frame table or packet
+// table by the rules of pm_rows_packets.h, one workgroup gives the accepted packets their places, and a fixed grid of waves builds the
+// pm_packet rows that pm_codec_fetch would hand out; a row whose table does not say everything about it is named with the reason.
 #include "pm_common.h"
 #include "pm_bitscan_addrs.h"
 #include "pm_bitscan_events.h"
 #include "pm_bitscan_frames.h"
 #include "pm_bitscan_rows.h"
 #include "pm_il2p_core.h"
+#include "pm_rows_packets.h"
 #include <algorithm>
 #include <cstring>
 
@@ -561,6 +565,31 @@ __global__ __launch_bounds__(kLanes) void bitscan_emit_kernel(Jobs J, uint8_t *b
                 copies[jb.ev0 + at + k] = make_uint2(listed_P(l, k), jb.started && listed_F(l, k) == 0xFFFFFFFFu ? kNotMade : (l.nothing >> k) & 1 ? kClosesNothing : listed_F(l, k));
 }
 
+// The CRC-16 of pm_bitscan_frames.h across a wave, for the frames launch and for pm_rows_packets' build launch: the 256 one-byte steps into
+// LDS (crc_functions.py:44-55, eight bits at a time), and the register behind `len` >= 2 bytes that follow the register `crc`: 64 pieces
+// that end at the last byte, a lane a piece, joined by a scan with powers of x.
+__device__ inline void wave_crc_table(uint16_t *crc_table, int lane)
+{
+    for (int v = lane; v < 256; v += 64) {
+        unsigned c = (unsigned)v;
+        for (int i = 0; i < 8; ++i) c = (c & 1) ? (c >> 1) ^ 0x8408u : c >> 1;
+        crc_table[v] = (uint16_t)c;
+    }
+}
+template <class Byte>
+__device__ inline uint32_t wave_crc(const uint16_t *crc_table, int lane, int len, uint32_t crc, Byte byte)
+{
+    using namespace pm_frames;
+    const int per = (len + 63) >> 6;
+    uint32_t piece = crc_piece(crc_table, lane, len, per, crc, byte), f = crc_times_x(0x8000u, 8 * per);
+    for (int dl = 1; dl < 64; dl <<= 1) {
+        const uint32_t o = __shfl_up(piece, dl);
+        if (lane >= dl) piece ^= crc_mul(f, o);
+        f = crc_mul(f, f);
+    }
+    return __shfl(piece, 63);
+}
+
 // Launch 4 (pm_scan_job.frames): a wave per listed flag {P, F} -- the events e, e + waves, ... of its job, the count read from the combine
 // launch's device-side copy -- writes the frame that ends there.  The span from F (or the stream's start) to P is taken `frame_words`
 // words per trip, a lane a word: the lane's word as the counters see it (pm_bitscan_frames.h), a scan over the lanes for the counters in
@@ -581,11 +610,7 @@ __global__ __launch_bounds__(64) void bitscan_frames_kernel(Jobs J, uint8_t *blo
     const int64_t n = jb.n, cap = n / 19 + 2;
     const int32_t count = (int32_t)(counts[j] < cap ? counts[j] : cap);
     if ((int)blockIdx.x >= count) return;
-    for (int v = lane; v < 256; v += 64) {
-        unsigned c = (unsigned)v;
-        for (int i = 0; i < 8; ++i) c = (c & 1) ? (c >> 1) ^ 0x8408u : c >> 1;      // crc_functions.py:44-55, eight bits at a time
-        crc_table[v] = (uint16_t)c;
-    }
+    wave_crc_table(crc_table, lane);
     const uint8_t *d = jb.data;
     uint8_t *table = block + jb.off + PM_SCAN_HEAD + list_bytes(0, n) + ((n + 7) & ~int64_t(7)), *area = table + PM_SCAN_FRAME_TABLE_BYTES(n);
     const int fw = J.frame_words;
@@ -658,14 +683,7 @@ __global__ __launch_bounds__(64) void bitscan_frames_kernel(Jobs J, uint8_t *blo
                 if (len == 1) {
                     crc = (crc >> 8) ^ crc_table[(crc ^ byte(0)) & 0xFF];
                 } else if (len >= 2) {
-                    const int per = (len + 63) >> 6;
-                    uint32_t piece = crc_piece(crc_table, lane, len, per, crc, byte), f = crc_times_x(0x8000u, 8 * per);
-                    for (int dl = 1; dl < 64; dl <<= 1) {
-                        const uint32_t o = __shfl_up(piece, dl);
-                        if (lane >= dl) piece ^= crc_mul(f, o);
-                        f = crc_mul(f, f);
-                    }
-                    crc = __shfl(piece, 63);
+                    crc = wave_crc(crc_table, lane, len, crc, byte);
                 }
                 if (nb >= 2) {
                     held0 = (line[(sh + nb - 2) >> 2] >> (8 * ((sh + nb - 2) & 3))) & 0xFF;
@@ -980,6 +998,188 @@ __global__ __launch_bounds__(kLanes) void rows_carry_start_kernel(pm_rows_carry 
     carries[row0 + r] = v;
 }
 
+// ---- pm_rows_packets: finished pm_packet rows from the rows' scan parts, behind pm_rows_scan (the rules: pm_rows_packets.h) -------------------
+// What the three launches know of the call: the chains by value, the rows' records and steps.  Where a row's part lies in the block follows
+// from the records as in rows_prepare_kernel, with the same limits: a row that the scan left out is left out here.
+struct RowPk {
+    const pm_rowslice_rec *recs;
+    const uint16_t *steps;
+    int64_t cap, row0;
+    int32_t nrows, nchains, tile_words;
+    int8_t kind[pm_rows::kMaxChains], frames[pm_rows::kMaxChains], packets[pm_rows::kMaxChains], addrs[pm_rows::kMaxChains], tol[pm_rows::kMaxChains];
+    uint8_t pkopt[pm_rows::kMaxChains];
+    int32_t source[pm_rows::kMaxChains];
+};
+struct RowPkInfo {                          // the walk launch's note of a row for the build launch
+    int64_t scan;                           // the row's scan part in the block (behind its steps), -1: left out
+    int64_t acc0;                           // the row's first place in the accepted list
+    int32_t n, reserved;
+};
+constexpr int kBuildWaves = 1024;           // waves that share a call's packets in the build launch
+
+// Launch 1: a lane a row.  A workgroup first adds up the sums of the rows in front of its own (a lane 16 rows at the most), then scans its
+// 256 rows as the prepare launch does: the row's part, and its place in the accepted list -- the events and places in front of it, of
+// which a row accepts no more than it has.  Then the row's rule.
+__global__ __launch_bounds__(kLanes) void rows_packets_walk_kernel(RowPk K, const uint8_t *block, pm_rows_packets_entry *entries, RowPkInfo *info,
+                                                                   pm_rpk::Accepted *acc, pm_rows::Sums limit)
+{
+    using namespace pm_rows;
+    __shared__ Sums lds[kLanes];
+    const int r0 = (int)blockIdx.x * kLanes, t = (int)threadIdx.x;
+    auto add = [](const Sums &a, const Sums &b) { return sums_add(a, b); };
+    auto bytes_of = [&](int r) { return row_bytes(K.recs[K.row0 + r].count, K.cap); };
+    auto sums_of = [&](int r) {
+        const int c = (int)((K.row0 + r) % K.nchains);
+        const int64_t n = bytes_of(r);
+        return row_sums(K.kind[c], K.frames[c], K.packets[c], n < kMaxBytes ? n : kMaxBytes, K.tile_words, K.addrs[c]);
+    };
+    Sums front = sums_zero();
+    for (int r = t; r < r0; r += kLanes) front = sums_add(front, sums_of(r));
+    block_scan(front, lds, add);
+    front = lds[kLanes - 1];
+    __syncthreads();
+    const int r = r0 + t;
+    const bool active = r < K.nrows;
+    block_scan(active ? sums_of(r) : sums_zero(), lds, add);
+    const Sums before = sums_add(front, t ? lds[t - 1] : sums_zero());
+    if (!active) return;
+    const int c = (int)((K.row0 + r) % K.nchains), kind = K.kind[c];
+    const Entry e = row_entry(before, kind, K.frames[c], K.packets[c], bytes_of(r), K.tile_words, limit, K.addrs[c]);
+    pm_rows_packets_entry out{0, PM_ROWS_PACKETS_LEFT_OUT, 0, 0, 0, 0};
+    RowPkInfo ri{-1, before.events + before.places, e.n, 0};
+    if (e.off >= 0) {
+        ri.scan = e.off + steps_bytes(e.n);
+        const pm_rpk::Part p = pm_rpk::part_of(block + ri.scan, kind, e.n);
+        out.lfsr_state = pm_rpk::ld64(p.rec);
+        pm_rpk::Accepted *mine = acc + ri.acc0;
+        auto emit = [mine](int i, const pm_rpk::Accepted &a) { mine[i] = a; };
+        if (kind == 1) out.status = pm_rpk::il2p_walk(p, K.tol[c], K.pkopt[c] & 1, &out.packets, &out.corrected_left, emit);
+        else if (kind == 0) out.status = pm_rpk::ax25_walk(p, &out.packets, emit);
+        else out.status = PM_ROWS_PACKETS_NO_CODEC;
+        if (out.status != PM_ROWS_PACKETS_FINISHED) out.packets = out.corrected_left = 0;
+    }
+    entries[r] = out;
+    info[r] = ri;
+}
+
+// Launch 2: one workgroup, trips of 256 rows, a lane a row: an inclusive scan of the rows' counts over the lanes, the carry from trip to
+// trip.  A row whose packets would pass the capacity takes none, and no row behind it does (the sum only grows): NO_ROOM, at the total.
+__global__ __launch_bounds__(kLanes) void rows_packets_room_kernel(int nrows, pm_rows_packets_head *head, pm_rows_packets_entry *entries, int64_t capacity)
+{
+    __shared__ int64_t lds[kLanes];
+    __shared__ unsigned long long kept;     // the packets of the rows that have room
+    __shared__ int handed;
+    const int t = (int)threadIdx.x;
+    if (t == 0) {
+        kept = 0;
+        handed = 0;
+    }
+    __syncthreads();
+    int64_t carry = 0;
+    for (int r0 = 0; r0 < nrows; r0 += kLanes) {
+        const int r = r0 + t;
+        const bool active = r < nrows;
+        pm_rows_packets_entry e{0, 0, 0, 0, 0, 0};
+        if (active) e = entries[r];
+        const int64_t incl = carry + block_scan((int64_t)e.packets, lds, [](int64_t a, int64_t b) { return a + b; });
+        carry += lds[kLanes - 1];
+        const bool over = pm_rpk::no_room(incl, capacity);
+        if (active && !over) atomicMax(&kept, (unsigned long long)incl);
+        if (active && (over || e.status != PM_ROWS_PACKETS_FINISHED)) atomicAdd(&handed, 1);
+        __syncthreads();                    // (a row without room has no row with room behind it: `kept` is final for it)
+        if (active) {
+            e.first = over ? (int64_t)kept : incl - e.packets;
+            if (over) {
+                e.status = PM_ROWS_PACKETS_NO_ROOM;
+                e.packets = e.corrected_left = 0;
+            }
+            entries[r] = e;
+        }
+    }
+    __syncthreads();
+    if (t == 0) *head = pm_rows_packets_head{nrows, handed, (int64_t)kept};
+}
+
+// Launch 3: a fixed grid, a wave a workgroup; wave w takes the packets w, w + waves, ... up to the head's total.  The packet's row by binary
+// search over `first`; its bytes put together in LDS -- IL2P: the AX.25 header that lane 0 rebuilds from the 13 bytes in the area, the
+// payload a byte a lane, the CRC of both by the frames launch's join, the carried CRC from the Hamming-coded bytes behind the last block
+// or the computed one; AX.25: the frame from the area, its CRC from the table -- the address from the checkpoint in front and up to 63
+// steps, a lane a step; then the row's 1280 data bytes as whole words, zeros behind the packet, and its 40-byte head by lane 0
+// (pm_rpk::packet_build says the same for one thread).
+__global__ __launch_bounds__(64) void rows_packets_build_kernel(RowPk K, const uint8_t *block, uint8_t *out, const RowPkInfo *info, const pm_rpk::Accepted *acc)
+{
+    using namespace pm_rpk;
+    __shared__ uint64_t pkt64[PM_PKT_MAX / 8];
+    __shared__ uint16_t crc_table[256];
+    const int lane = (int)threadIdx.x;
+    uint8_t *pkt = reinterpret_cast<uint8_t *>(pkt64);
+    const pm_rows_packets_entry *entries = reinterpret_cast<const pm_rows_packets_entry *>(out + kHeadBytes);
+    uint8_t *rows = out + kHeadBytes + (size_t)kEntryBytes * (size_t)K.nrows;
+    const int64_t total = reinterpret_cast<const pm_rows_packets_head *>(out)->packets;
+    if ((int64_t)blockIdx.x >= total) return;
+    wave_crc_table(crc_table, lane);
+    for (int64_t q = (int64_t)blockIdx.x; q < total; q += (int64_t)gridDim.x) {
+        const int r = row_of_packet([entries](int i) { return entries[i].first; }, K.nrows, q);
+        const RowPkInfo ri = info[r];
+        const int c = (int)((K.row0 + r) % K.nchains), kind = K.kind[c];
+        const Accepted a = acc[ri.acc0 + (q - entries[r].first)];
+        const Part p = part_of(block + ri.scan, kind, ri.n);
+        __syncthreads();
+        for (int v = lane; v < PM_PKT_MAX / 8; v += 64) pkt64[v] = 0;
+        __syncthreads();
+        int len, calculated;
+        uint32_t carried;
+        int64_t k;
+        if (kind == 1) {
+            const pm_il2p::Rec rec = ld_rec(p, (int32_t)a.index);
+            const uint8_t *src = p.area + rec.off;
+            int hl = 0;
+            if (lane == 0) hl = pm_il2p::ax25_header(src, pkt);
+            hl = __shfl(hl, 0);
+            for (int v = lane; v < (int)rec.count; v += 64) pkt[hl + v] = src[13 + v];
+            __syncthreads();
+            const int body = hl + (int)rec.count;
+            uint32_t crc = 0xFFFF;
+            if (body == 1) crc = (crc >> 8) ^ crc_table[(crc ^ pkt[0]) & 0xFF];
+            else if (body >= 2) crc = wave_crc(crc_table, lane, body, crc, [pkt](int i) -> uint32_t { return pkt[i]; });
+            calculated = (int)((crc ^ 0xFFFF) & 0xFFFF);
+            int64_t E = (int64_t)a.bit + 1;
+            carried = (uint32_t)calculated;                 // il2p.py:427-431: without the trailing CRC the computed one is appended
+            if (K.pkopt[c] & 1) {
+                carried = (uint32_t)pm_il2p::hamming_crc(byte_at(p.plain, E), byte_at(p.plain, E + 8), byte_at(p.plain, E + 16), byte_at(p.plain, E + 24));
+                E += 32;
+            }
+            len = body + 2;
+            if (lane == 0) {
+                pkt[body] = (uint8_t)(carried & 0xFF);
+                pkt[body + 1] = (uint8_t)(carried >> 8);
+            }
+            k = (E - 1) >> 3;
+        } else {
+            const uint32_t F = ld32(p.list + 8 * (int64_t)a.index + 4);
+            const int64_t at = F == 0xFFFFFFFFu ? 0 : (int64_t)(F >> 3);
+            const int whole = (int32_t)ld32(p.table + 8 * (int64_t)a.index);
+            len = whole < PM_PKT_MAX ? whole : PM_PKT_MAX;  // (a frame longer than a row: its first bytes, the whole frame's CRCs)
+            calculated = (int)ld32(p.table + 8 * (int64_t)a.index + 4);
+            carried = (uint32_t)p.area[at + whole - 1] * 256u + p.area[at + whole - 2];
+            for (int v = lane; v < len; v += 64) pkt[v] = p.area[at + v];
+            k = (int64_t)(a.bit >> 3);
+        }
+        __syncthreads();
+        // pm_addrs::resolve across the wave: steps (k & ~63) + 1 .. k
+        const uint16_t *steps = K.steps + (K.row0 + r) * K.cap;
+        const int64_t i = (k & ~(int64_t)63) + 1 + lane;
+        uint32_t gone = i <= k ? steps[i] : 0u;
+        for (int dl = 32; dl; dl >>= 1) gone += __shfl_xor(gone, dl);
+        uint8_t *dst = rows + (size_t)q * sizeof(pm_packet);
+        for (int v = lane; v < PM_PKT_MAX / 8; v += 64) reinterpret_cast<uint64_t *>(dst + 40)[v] = pkt64[v];
+        if (lane == 0) {
+            const HeadWords h = head_words(p.addrs[k >> 6] + (int64_t)gone, pkt, len, a.corrected, calculated, carried, K.source[c]);
+            for (int v = 0; v < 5; ++v) reinterpret_cast<uint64_t *>(dst)[v] = h.w[v];
+        }
+    }
+}
+
 // what the launches share in context scratch, cut for `jobs` jobs (or rows)
 struct ScanScratch {
     TileSum *sums;
@@ -1259,6 +1459,78 @@ extern "C" int pm_rows_scan_pieces(pm_ctx *ctx, const pm_rowslice_rec *d_recs, c
     scan_launch(ctx, J, L, nrows, all.tiles, all.events, all.places, any, static_cast<uint8_t *>(d_block), s, kRowFrameWaves, kRowPacketWaves);
     if (any_addrs && all.tiles)
         hipLaunchKernelGGL(rows_addrs_kernel<RowPieceJobs>, dim3((unsigned)all.tiles), dim3(kLanes), 0, ctx->stream, L, static_cast<uint8_t *>(d_block), s.steps_before);
+    PM_HIP(hipGetLastError());
+    return PM_OK;
+}
+
+extern "C" int pm_rows_packets(pm_ctx *ctx, const pm_rowslice_rec *d_recs, const uint16_t *d_steps, int64_t cap, int64_t row0, int nrows,
+                               const pm_rows_scan_chain *h_chains, int nchains, const int32_t *h_sources, const int64_t *h_counts, const void *d_block,
+                               const int64_t *h_offsets, void *d_out, size_t out_bytes, size_t *h_used)
+{
+    using namespace pm_rows;
+    PM_CTX(ctx);
+    PM_ARG(d_recs && d_steps && cap >= 0 && (cap & 7) == 0 && ((uintptr_t)d_steps & 7) == 0 && row0 >= 0);
+    PM_ARG(nrows >= 1 && nrows <= kMaxRows && h_chains && nchains >= 1 && nchains <= kMaxChains && h_counts && h_offsets);
+    PM_ARG(d_block && ((uintptr_t)d_block & 7) == 0 && d_out && ((uintptr_t)d_out & 7) == 0 && h_used);
+    RowPk K;
+    memset(&K, 0, sizeof(K));
+    K.recs = d_recs;
+    K.steps = d_steps;
+    K.cap = cap;
+    K.row0 = row0;
+    K.nrows = nrows;
+    K.nchains = nchains;
+    const int tune = ctx->tune.bitscan_tile_words;
+    K.tile_words = tune > 0 ? std::min(tune, kLanes) : kLanes;
+    for (int c = 0; c < nchains; ++c) {
+        const pm_rows_scan_chain &q = h_chains[c];
+        PM_ARG(q.codec_kind >= -1 && q.codec_kind <= 1);
+        PM_ARG(q.frames == 0 || (q.frames == 1 && q.codec_kind == 0));
+        PM_ARG(q.packets == 0 || (q.packets == 1 && q.codec_kind == 1));
+        PM_ARG(q.addrs == 0 || q.addrs == 1);
+        // a chain with a codec goes this way by the table of its kind and the checkpoints
+        PM_ARG(q.codec_kind < 0 || (q.addrs == 1 && (q.codec_kind == 0 ? q.frames : q.packets) == 1));
+        K.kind[c] = (int8_t)q.codec_kind;
+        K.frames[c] = (int8_t)q.frames;
+        K.packets[c] = (int8_t)q.packets;
+        K.addrs[c] = (int8_t)q.addrs;
+        K.tol[c] = (int8_t)std::max(-1, std::min(33, q.sync_tol));
+        K.pkopt[c] = (uint8_t)(q.il2p_crc != 0);
+        K.source[c] = h_sources ? h_sources[c] : c;
+    }
+    // the sums as pm_rows_scan made them from the same counts: the limits of the device's own table, and what the offsets must be
+    Sums all = sums_zero();
+    for (int r = 0; r < nrows; ++r) {
+        const pm_rows_scan_chain &q = h_chains[(row0 + r) % nchains];
+        const int64_t n = h_counts[r];
+        PM_ARG(n >= 0 && n <= cap && n <= kMaxBytes && h_offsets[r] == all.off);
+        all = sums_add(all, row_sums(q.codec_kind, q.frames, q.packets, n, K.tile_words, q.addrs));
+        PM_ARG(all.tiles < (int64_t)1 << 30);
+    }
+    // these launches read the block: it must be memory of the device's
+    {
+        hipPointerAttribute_t attr;
+        memset(&attr, 0, sizeof(attr));
+        const hipError_t e = hipPointerGetAttributes(&attr, d_block);
+        if (e != hipSuccess) (void)hipGetLastError();
+        if (e != hipSuccess || (attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeManaged))
+            return pm_set_error(PM_ERR_ARG, "pm_rows_packets: d_block is not device memory (the launches read it)");
+    }
+    const size_t front = (size_t)pm_rpk::kHeadBytes + (size_t)pm_rpk::kEntryBytes * (size_t)nrows;
+    *h_used = front;
+    if (out_bytes < front) return pm_set_error(PM_ERR_CAPACITY, "pm_rows_packets: d_out holds %zu bytes, head and entries need %zu", out_bytes, front);
+    const int64_t capacity = (int64_t)((out_bytes - front) / sizeof(pm_packet));
+    const size_t info_bytes = ((size_t)nrows * sizeof(RowPkInfo) + 63) & ~(size_t)63;
+    if (int rc = pm_scratch_reserve(ctx, info_bytes + (size_t)(all.events + all.places) * sizeof(pm_rpk::Accepted) + 64)) return rc;
+    RowPkInfo *info = static_cast<RowPkInfo *>(ctx->d_scratch);
+    pm_rpk::Accepted *acc = reinterpret_cast<pm_rpk::Accepted *>(static_cast<uint8_t *>(ctx->d_scratch) + info_bytes);
+    uint8_t *out = static_cast<uint8_t *>(d_out);
+    pm_rows_packets_head *head = reinterpret_cast<pm_rows_packets_head *>(out);
+    pm_rows_packets_entry *entries = reinterpret_cast<pm_rows_packets_entry *>(out + pm_rpk::kHeadBytes);
+    hipLaunchKernelGGL(rows_packets_walk_kernel, dim3((unsigned)pm_cdiv(nrows, kLanes)), dim3(kLanes), 0, ctx->stream, K, static_cast<const uint8_t *>(d_block), entries,
+                       info, acc, all);
+    hipLaunchKernelGGL(rows_packets_room_kernel, dim3(1), dim3(kLanes), 0, ctx->stream, nrows, head, entries, capacity);
+    hipLaunchKernelGGL(rows_packets_build_kernel, dim3(kBuildWaves), dim3(64), 0, ctx->stream, K, static_cast<const uint8_t *>(d_block), out, info, acc);
     PM_HIP(hipGetLastError());
     return PM_OK;
 }

@@ -60,6 +60,15 @@ PM_AD_HD uint32_t piece_lane_sum(uint64_t lo, uint64_t hi, int64_t w, int64_t n)
 }
 PM_AD_HD uint32_t piece_lane_first(uint64_t lo) { return (uint32_t)(lo & 0xFFFFu); }
 
+// the address of byte k from the checkpoint in front of it and at most 63 of the stream's steps (A and steps aligned: device memory, or a
+// host copy that is)
+PM_AD_HD int64_t resolve(const int64_t *A, const uint16_t *steps, int64_t k)
+{
+    int64_t a = A[k >> 6];
+    for (int64_t i = (k & ~(int64_t)63) + 1; i <= k; ++i) a += steps[i];
+    return a;
+}
+
 // ---- the host's side --------------------------------------------------------------------------------------------------------------------
 // One stream's table and steps; [k]: the address of byte k.  Counts what it did (pm_codec_addr_work).
 struct Lookup {

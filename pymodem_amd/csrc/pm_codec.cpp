@@ -27,6 +27,7 @@
 #include "../../include/pymodem_amd.h"
 #include "pm_bitscan_addrs.h"
 #include "pm_il2p_core.h"
+#include "pm_rows_packets.h"
 
 int pm_set_error(int code, const char *fmt, ...);
 
@@ -52,16 +53,8 @@ int crc16(const uint8_t *d, int64_t n)
     return (int)(crc ^ 0xFFFF);
 }
 
-// packet_meta.py:21-41.  The loop there never resets its sub-field index, so only bytes 0..6 are examined.
-bool valid_header(const uint8_t *d, int len)
-{
-    if (len <= 15) return false;
-    for (int k = 0; k < 7; ++k) {
-        const int ch = d[k] >> 1;
-        if ((ch < 32 || ch > 126) && ch != 0) return false;
-    }
-    return true;
-}
+// packet_meta.py:21-41: pm_rows_packets.h, shared with pm_rows_packets' build launch
+bool valid_header(const uint8_t *d, int len) { return pm_rpk::valid_header(d, len); }
 
 // crc: the frame's calculated CRC if whoever queued it knows it (pm_stream_scan's frame table), -1: computed here
 void finalize(pm_packet &p, int crc = -1)
@@ -587,14 +580,6 @@ struct Ax25 : pm_codec {
     }
 };
 
-const uint8_t kHamming74[128] = {   // il2p.py:23-40
-    0x0, 0x0, 0x0, 0x3, 0x0, 0x5, 0xe, 0x7, 0x0, 0x9, 0xe, 0xb, 0xe, 0xd, 0xe, 0xe, 0x0, 0x3, 0x3, 0x3, 0x4, 0xd, 0x6, 0x3,
-    0x8, 0xd, 0xa, 0x3, 0xd, 0xd, 0xe, 0xd, 0x0, 0x5, 0x2, 0xb, 0x5, 0x5, 0x6, 0x5, 0x8, 0xb, 0xb, 0xb, 0xc, 0x5, 0xe, 0xb,
-    0x8, 0x1, 0x6, 0x3, 0x6, 0x5, 0x6, 0x6, 0x8, 0x8, 0x8, 0xb, 0x8, 0xd, 0x6, 0xf, 0x0, 0x9, 0x2, 0x7, 0x4, 0x7, 0x7, 0x7,
-    0x9, 0x9, 0xa, 0x9, 0xc, 0x9, 0xe, 0x7, 0x4, 0x1, 0xa, 0x3, 0x4, 0x4, 0x4, 0x7, 0xa, 0x9, 0xa, 0xa, 0x4, 0xd, 0xa, 0xf,
-    0x2, 0x1, 0x2, 0x2, 0xc, 0x5, 0x2, 0x7, 0xc, 0x9, 0x2, 0xb, 0xc, 0xc, 0xc, 0xf, 0x1, 0x1, 0x2, 0x1, 0x4, 0x1, 0x6, 0xf,
-    0x8, 0x1, 0xa, 0xf, 0xc, 0xf, 0xf, 0xf};
-
 struct Il2p : pm_codec {
     enum State { kSync, kHeader, kBig, kSmall, kCrc };
     bool want_crc, disable_rs;
@@ -697,8 +682,7 @@ struct Il2p : pm_codec {
             header();
             data.insert(data.end(), pk_area + r.off + 13, pk_area + r.off + 13 + r.count);
             if (want_crc) {
-                int c = 0;
-                for (int q = 0; q < 4; ++q) c += kHamming74[byte_at(E + 8 * q) & 0x7F] << (12 - 4 * q);     // il2p.py:509-512
+                const int c = hamming_crc(byte_at(E), byte_at(E + 8), byte_at(E + 16), byte_at(E + 24));     // il2p.py:509-512, pm_il2p_core.h
                 E += 32;
                 data.push_back((uint8_t)(c & 0xFF));
                 data.push_back((uint8_t)(c >> 8));
@@ -864,49 +848,14 @@ struct Il2p : pm_codec {
         }
     }
 
-    // il2p.py:214-344: unpack the 13 header bytes and rebuild the AX.25 header.  Returns the payload byte count.
+    // il2p.py:214-344: unpack the 13 header bytes and rebuild the AX.25 header (pm_il2p_core.h, shared with pm_rows_packets).  Returns the
+    // payload byte count.
     int header()
     {
-        const uint8_t *b = buf;
-        const int type = (b[1] & 0x80) >> 7;
-        int count = 0, pid = 0, ctl = 0;
-        for (int i = 0; i < 10; ++i)
-            if (b[i + 2] & 0x80) count |= 0x200 >> i;
-        for (int i = 0; i < 4; ++i)
-            if (b[i + 1] & 0x40) pid |= 0x8 >> i;
-        for (int i = 0; i < 7; ++i)
-            if (b[i + 5] & 0x40) ctl |= 0x40 >> i;
-        enum { UI, S, U, I } kind = (b[0] & 0x40) ? UI : (pid == 0 ? S : (pid == 1 ? U : I));
-        static const uint8_t pid_table[16] = {0, 0, 0x10, 0x01, 0x06, 0x07, 0x08, 0xC3, 0xC4, 0xCA, 0xCB, 0xCC, 0xCD, 0xCE, 0xCF, 0xF0};
-        const bool pf = ctl & 0x40;
-        bool cbit = false;
-        int nr = 0, ns = 0, op = 0;
-        if (kind == I) {
-            ns = ctl & 0x7;
-            nr = (ctl >> 3) & 0x7;
-            cbit = true;
-        } else if (kind == S) {
-            nr = (ctl >> 3) & 0x7;
-            cbit = ctl & 0x4;
-            op = ctl & 0x3;
-        } else {
-            cbit = ctl & 0x4;
-            op = (ctl >> 3) & 0x7;
-        }
-        if (type == 1) {                                     // il2p.py:292-340
-            for (int i = 0; i < 6; ++i) data.push_back((uint8_t)(((b[i] & 0x3F) + 0x20) << 1));
-            data.push_back((uint8_t)(((b[12] >> 4) << 1) + 0x60 + (cbit ? 0x80 : 0)));
-            for (int i = 0; i < 6; ++i) data.push_back((uint8_t)(((b[i + 6] & 0x3F) + 0x20) << 1));
-            data.push_back((uint8_t)(((b[12] & 0xF) << 1) + 0x60 + (cbit ? 0 : 0x80) + 1));
-            static const uint8_t u_control[8] = {0x2F, 0x43, 0x0F, 0x63, 0x87, 0x03, 0xAF, 0xE3};
-            int cb;
-            if (kind == U || kind == UI) cb = u_control[op] | (pf ? 0x10 : 0);
-            else if (kind == S) cb = 0x1 | (op << 2) | (nr << 5) | (pf ? 0x10 : 0);
-            else cb = (ns << 1) | (nr << 5) | (pf ? 0x10 : 0);
-            data.push_back((uint8_t)cb);
-            if (pid_table[pid] != 0) data.push_back(pid_table[pid]);
-        }                                                    // type 0: transparent encapsulation, nothing added
-        return count;
+        uint8_t ax[16];
+        const int len = pm_il2p::ax25_header(buf, ax);
+        data.insert(data.end(), ax, ax + len);
+        return pm_il2p::header_count(buf);
     }
 
     void feed(uint8_t byte, int64_t addr, Sink &sink) override { feed_bits(byte, 8, addr, sink); }
@@ -983,8 +932,7 @@ struct Il2p : pm_codec {
             case kCrc: {
                 if (nbuf != 4) break;
                 nbuf = 0;
-                int c = 0;
-                for (int k = 0; k < 4; ++k) c += kHamming74[buf[k] & 0x7F] << (12 - 4 * k);     // il2p.py:509-512
+                const int c = pm_il2p::hamming_crc(buf[0], buf[1], buf[2], buf[3]);     // il2p.py:509-512, pm_il2p_core.h
                 data.push_back((uint8_t)(c & 0xFF));
                 data.push_back((uint8_t)(c >> 8));
                 emit(addr, sink);

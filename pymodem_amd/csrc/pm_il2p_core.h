@@ -1,6 +1,7 @@
 // What an IL2P decoder does behind a sync word, in the pieces that the host decoder (pm_codec.cpp) and pm_stream_scan's packets launches
 // (pm_bitscan.hip) share: GF(2^8), the Reed-Solomon decoder of rs_functions.py:33-150, the descrambler of il2p.py:160-163, the header's
-// payload count and the block split of il2p.py:346-358, and the record of an ATTEMPT -- what Il2p::feed_bits does from the bit H at which
+// payload count and the block split of il2p.py:346-358, the AX.25 header that a decoded IL2P header stands for (il2p.py:214-344) and the
+// Hamming(7,4) table of the trailing CRC (for the host decoder and pm_rows_packets' build launch), and the record of an ATTEMPT -- what Il2p::feed_bits does from the bit H at which
 // it enters kHeader until it is back in kSync, which depends on nothing but the descrambled bits from H on and the codec's options.
 // Compiles for the host and the device; the tables come through a pointer (an object on the host, LDS on the device).  The serial parts
 // (Berlekamp, Forney, the serial Chien search and syndromes) are the host's own statements; what the blocks launch restates for lanes --
@@ -232,8 +233,67 @@ PM_IL2P_HD inline int header_count(const uint8_t *b)        // il2p.py:214-290, 
     return count;
 }
 
+// il2p.py:214-344: the AX.25 header that the 13 descrambled header bytes stand for, into out (16 bytes at the most); returns how many.
+// Type 0 is transparent encapsulation: nothing.  The two small tables are packed into words, a byte an entry: no table in memory.
+PM_IL2P_HD inline int ax25_header(const uint8_t *b, uint8_t *out)
+{
+    const int type = (b[1] & 0x80) >> 7;
+    int pid = 0, ctl = 0;
+    for (int i = 0; i < 4; ++i)
+        if (b[i + 1] & 0x40) pid |= 0x8 >> i;
+    for (int i = 0; i < 7; ++i)
+        if (b[i + 5] & 0x40) ctl |= 0x40 >> i;
+    enum { UI, S, U, I } kind = (b[0] & 0x40) ? UI : (pid == 0 ? S : (pid == 1 ? U : I));
+    // {0, 0, 0x10, 0x01, 0x06, 0x07, 0x08, 0xC3, 0xC4, 0xCA, 0xCB, 0xCC, 0xCD, 0xCE, 0xCF, 0xF0}
+    const unsigned pid_byte = (unsigned)((pid < 8 ? 0xC308070601100000ull : 0xF0CFCECDCCCBCAC4ull) >> (8 * (pid & 7))) & 0xFF;
+    const bool pf = ctl & 0x40;
+    bool cbit = false;
+    int nr = 0, ns = 0, op = 0;
+    if (kind == I) {
+        ns = ctl & 0x7;
+        nr = (ctl >> 3) & 0x7;
+        cbit = true;
+    } else if (kind == S) {
+        nr = (ctl >> 3) & 0x7;
+        cbit = ctl & 0x4;
+        op = ctl & 0x3;
+    } else {
+        cbit = ctl & 0x4;
+        op = (ctl >> 3) & 0x7;
+    }
+    if (type != 1) return 0;
+    int at = 0;                                             // il2p.py:292-340
+    for (int i = 0; i < 6; ++i) out[at++] = (uint8_t)(((b[i] & 0x3F) + 0x20) << 1);
+    out[at++] = (uint8_t)(((b[12] >> 4) << 1) + 0x60 + (cbit ? 0x80 : 0));
+    for (int i = 0; i < 6; ++i) out[at++] = (uint8_t)(((b[i + 6] & 0x3F) + 0x20) << 1);
+    out[at++] = (uint8_t)(((b[12] & 0xF) << 1) + 0x60 + (cbit ? 0 : 0x80) + 1);
+    int cb;
+    // {0x2F, 0x43, 0x0F, 0x63, 0x87, 0x03, 0xAF, 0xE3}
+    if (kind == U || kind == UI) cb = (int)((0xE3AF0387630F432Full >> (8 * op)) & 0xFF) | (pf ? 0x10 : 0);
+    else if (kind == S) cb = 0x1 | (op << 2) | (nr << 5) | (pf ? 0x10 : 0);
+    else cb = (ns << 1) | (nr << 5) | (pf ? 0x10 : 0);
+    out[at++] = (uint8_t)cb;
+    if (pid_byte != 0) out[at++] = (uint8_t)pid_byte;
+    return at;
+}
+
+// il2p.py:23-40, the Hamming(7,4) decode table: 128 entries of four bits, sixteen to a word
+PM_IL2P_HD inline unsigned hamming74(unsigned v)
+{
+    v &= 0x7F;
+    const unsigned q = v >> 4;
+    const uint64_t w = q == 0 ? 0xEEDEBE907E503000ull : q == 1 ? 0xDEDD3AD836D43330ull : q == 2 ? 0xBE5CBBB85655B250ull : q == 3 ? 0xF6D8B88866563618ull
+                     : q == 4 ? 0x7E9C9A9977747290ull : q == 5 ? 0xFAD4AA9A74443A14ull : q == 6 ? 0xFCCCB29C725C2212ull : 0xFFFCFA18F6141211ull;
+    return (unsigned)(w >> (4 * (v & 15))) & 0xF;
+}
+// il2p.py:509-512: the CRC that four Hamming-coded bytes carry
+PM_IL2P_HD inline int hamming_crc(unsigned b0, unsigned b1, unsigned b2, unsigned b3)
+{
+    return (int)(hamming74(b0) << 12) + (int)(hamming74(b1) << 8) + (int)(hamming74(b2) << 4) + (int)hamming74(b3);
+}
+
 struct Split {
-    int blocks, size, big;                                  // il2p.py:346-358: `big` blocks of size + 1 bytes first, then blocks - big of `size`
+    int blocks, size, big;                                // il2p.py:346-358: `big` blocks of size + 1 bytes first, then blocks - big of `size`
 };
 PM_IL2P_HD inline Split block_split(int count)
 {

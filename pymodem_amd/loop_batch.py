@@ -373,14 +373,7 @@ class SlicedRun:
         recs = self.records()[row0:row0 + nrows]
         counts = np.ascontiguousarray(np.minimum(recs["count"], self.cap), dtype=np.int64)
         nchains = len(chains)
-        desc = (N.RowsScanChain * nchains)()
-        for d, ch in zip(desc, chains):
-            lfsr, codec = ch[3], ch[4]
-            d.lfsr_poly, d.lfsr_state, d.lfsr_invert = lfsr.polynomial, lfsr.shift_register, int(bool(lfsr.invert))
-            d.codec_kind, d.sync_tol = int(codec._kind), int(codec.sync_tolerance)
-            d.frames, d.packets = int(bool(frames) and codec._kind == 0), int(bool(packets) and codec._kind == 1)
-            d.il2p_crc, d.il2p_disable_rs, d.il2p_min_dist = int(codec.collect_trailing_crc), int(codec.disable_rs), int(codec.min_distance)
-            d.addrs = int(bool(addrs))
+        desc = _scan_desc(chains, frames, packets, addrs)
         of = [desc[(row0 + k) % nchains] for k in range(nrows)]
         parts = [N.scan_part_bytes(d.codec_kind, d.frames, d.packets, int(c), d.addrs) for d, c in zip(of, counts)]
         used = int(sum(N.rows_scan_steps_bytes(int(c)) for c in counts) + sum(parts))
@@ -400,6 +393,63 @@ class SlicedRun:
             sw = N.rows_scan_steps_bytes(c)
             out.append((host[o:o + 2 * c].view(np.uint16), int(recs["first_addr"][k]), c, host[o + sw:o + sw + parts[k]]))
         return out
+
+    def fetch_packets(self, row0, nrows, chains, copy_ctx=None, tag=None, sources=None, desc=None):
+        """fetch_scanned() with the codecs' work on the device as well (pm_rows_scan into a DEVICE block, pm_rows_packets behind it): the rows
+        of whole recordings -- row0 and nrows multiples of len(chains) -- with frames, packets and addrs on.  sources: what goes into
+        pm_packet.source_decoder per chain (None: 0, as a codec without chain ids stamps it).
+        -> (entries, packet rows, handed): the call's pm_rows_packets_entry per row and its pm_packet rows as host arrays -- a FINISHED row's
+        packets are rows[first:first + packets], and a recording's rows lie chain after chain -- and, for every recording with a row that is
+        not FINISHED, handed[index of its first row in the call] = what fetch_scanned returns for its rows, for _host_rows_scanned.
+        At most two copies to the host, head and entries, then exactly the packet rows, and one more per handed recording: its
+        consecutive parts of the scan block.  desc: the chains' pm_rows_scan_chain made earlier (_scan_desc with frames, packets and addrs
+        on), for a caller whose chain objects move on while the groups of a run are fetched."""
+        ctx = copy_ctx or self.ctx
+        nchains = len(chains)
+        assert row0 % nchains == 0 and nrows % nchains == 0, "whole recordings"
+        recs = self.records()[row0:row0 + nrows]
+        counts = np.ascontiguousarray(np.minimum(recs["count"], self.cap), dtype=np.int64)
+        desc = _scan_desc(chains, True, True, True) if desc is None else desc
+        of = [desc[k % nchains] for k in range(nrows)]
+        parts = [N.scan_part_bytes(d.codec_kind, d.frames, d.packets, int(c), d.addrs) for d, c in zip(of, counts)]
+        sizes = [N.rows_scan_steps_bytes(int(c)) + p for c, p in zip(counts, parts)]
+        used = int(sum(sizes))
+        key = tag if tag is not None else ("sliced-run", id(self))
+        room = (used + (8 << 20) - 1) // (8 << 20) * (8 << 20)
+        block = ctx.scratch((key, "scanned"), room, np.uint8)
+        offs, need = (ctypes.c_int64 * nrows)(), ctypes.c_size_t()
+        h_counts = counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+        check(lib().pm_rows_scan(ctx.handle, self.recs.ptr, self.data.ptr, self.steps.ptr, self.cap, row0, nrows, desc, nchains, h_counts, block.ptr, block.n,
+                                 offs, ctypes.byref(need)))
+        assert need.value == used, "pm_rows_scan and _native.scan_part_bytes size a row alike"
+        # (room for two packets a row and a few more: a row that finds none goes the existing way, whatever the room)
+        front, capacity = N.rows_packets_bytes(nrows), 2 * nrows + 64
+        out = ctx.scratch((key, "packets"), N.rows_packets_bytes(nrows, capacity), np.uint8)
+        h_sources = (ctypes.c_int32 * nchains)(*([0] * nchains if sources is None else [int(v) for v in sources]))
+        check(lib().pm_rows_packets(ctx.handle, self.recs.ptr, self.steps.ptr, self.cap, row0, nrows, desc, nchains, h_sources, h_counts, block.ptr, offs,
+                                    out.ptr, out.n, ctypes.byref(need)))
+        lead = out.download(front, ctx=ctx)
+        head = lead[:N.ROWS_PACKETS_HEAD_BYTES].view(N.rows_packets_head_dtype())[0]
+        entries = lead[N.ROWS_PACKETS_HEAD_BYTES:].view(N.rows_packets_entry_dtype())
+        total = int(head["packets"])
+        rows = out.view(front, total * N.packet_dtype().itemsize).download(ctx=ctx).view(N.packet_dtype()) if total else np.zeros(0, dtype=N.packet_dtype())
+        copied = front + rows.nbytes
+        handed = {}
+        for k in range(0, nrows, nchains):
+            if (entries["status"][k:k + nchains] == 0).all():
+                continue
+            lo = int(offs[k])
+            host = block.view(lo, sum(sizes[k:k + nchains])).download(ctx=ctx)
+            copied += host.nbytes
+            mine = []
+            for j in range(k, k + nchains):
+                c, o = int(counts[j]), int(offs[j]) - lo
+                sw = N.rows_scan_steps_bytes(c)
+                mine.append((host[o:o + 2 * c].view(np.uint16), int(recs["first_addr"][j]), c, host[o + sw:o + sw + parts[j]]))
+            handed[k] = mine
+        with self._copied_lock:
+            self.copied += copied
+        return entries, rows, handed
 
     def pieces(self, chains, frames=False, packets=False, addrs=False):
         """The rows of this run scanned piece by piece (pm_rows_scan_pieces), a device carry per row: -> RowPieces.  `chains`, frames, packets
@@ -532,6 +582,19 @@ class RowPieces:
         with self._lock:
             self.ordinary += int(count)
 
+
+
+def _scan_desc(chains, frames, packets, addrs):
+    """pm_rows_scan_chain for each of a run's chains [name, modem, slicer, stream, codec], from where their LFSR registers stand"""
+    desc = (N.RowsScanChain * len(chains))()
+    for d, ch in zip(desc, chains):
+        lfsr, codec = ch[3], ch[4]
+        d.lfsr_poly, d.lfsr_state, d.lfsr_invert = lfsr.polynomial, lfsr.shift_register, int(bool(lfsr.invert))
+        d.codec_kind, d.sync_tol = int(codec._kind), int(codec.sync_tolerance)
+        d.frames, d.packets = int(bool(frames) and codec._kind == 0), int(bool(packets) and codec._kind == 1)
+        d.il2p_crc, d.il2p_disable_rs, d.il2p_min_dist = int(codec.collect_trailing_crc), int(codec.disable_rs), int(codec.min_distance)
+        d.addrs = int(bool(addrs))
+    return desc
 
 
 _ENGINES = {}
@@ -696,7 +759,7 @@ def _beside(eng, chain_sets, dev, ctx, k, rows, chain_ids, stages, slot, frames,
 
 
 def process_recordings_device(chain_sets, audios, ctx=None, chunk=0, rows=False, chain_ids=None, stages=None, slot=0, defer=False, scan=None,
-                              frames=None, packets=None, addrs=None, pieces=None, beside=None):
+                              frames=None, packets=None, addrs=None, pieces=None, beside=None, rows_packets=None):
     """chain_sets[k] = the chains [name, modem, slicer, stream, codec] of recording k (every recording brings the same group of
     chains, as a service decoding successive recordings with one config does), audios[k] its int16 samples (host array or
     DeviceBuffer; equal lengths).  -> [[packets of chain 0, ...] per recording], identical to chain_execute.process_chain on each
@@ -724,7 +787,16 @@ def process_recordings_device(chain_sets, audios, ctx=None, chunk=0, rows=False,
     the run is to be redone from sign bitmaps: the chains' LFSR registers go back to what they were, the native codecs that the pieces fed
     are dropped (never fed, as at entry), the rows gathered are discarded, stages["beside"] = {"gave_up": t}.  Ignored where pieces is
     ignored (stages["beside"] = False).  Results are the same; stages["beside"] = {"every": k, "chunks": the run's, "marks": [those taken],
-    "seeds", "ordinary", "bytes_before_end": slicer bytes decoded from pieces in front of the final one}."""
+    "seeds", "ordinary", "bytes_before_end": slicer bytes decoded from pieces in front of the final one}.
+    rows_packets (None: the context's switch pipe_rows_packets, PM_PIPE_ROWS_PACKETS, default 0; implies scan, frames, packets and addrs;
+    ignored where pieces is ignored; not together with pieces or beside): the packets of every row whose tables say everything about it are
+    finished on the device (SlicedRun.fetch_packets: pm_rows_packets behind pm_rows_scan) and come to the host as pm_packet rows; a
+    recording whose rows are all FINISHED makes no codec and no host job -- its result is views of the copied array (rows=True) or
+    rows_to_packets of them, its chains' LFSR registers are set from the entries, its slicer states as ever.  The one visible difference:
+    its codec objects are left NEVER FED, in the state they were made in (the other routes leave them as the decoder stands behind the
+    recording).  A recording with a row that is handed over (bail, short row, a sync hit without a record, ...) is decoded the existing
+    way from its parts of the scan block.  Results are the same; stages["rows_packets"] = {"rows", "finished", "handed": {reason: rows},
+    "copied_bytes"} (False where ignored)."""
     from .chain_execute import _host_rows, _host_rows_pieces, _host_rows_scanned, _host_stages, _host_stages_scanned, _pool
     from .slicer import slice_batch
     ctx = ctx or Context.default()
@@ -745,6 +817,11 @@ def process_recordings_device(chain_sets, audios, ctx=None, chunk=0, rows=False,
     if beside and pieces is not None:
         raise ValueError("process_recordings_device: beside and pieces are two ways to cut the same rows; one of them")
     scan = scan or bool(beside)
+    rows_packets = bool(ctx.tuned("pipe_rows_packets")) if rows_packets is None else bool(rows_packets)
+    if rows_packets and (beside or pieces is not None):
+        raise ValueError("process_recordings_device: rows_packets finishes whole rows; not together with pieces or beside")
+    if rows_packets:
+        scan = frames = packets = addrs = True
     gave_up = None
     dev = []
     for a in audios:
@@ -806,6 +883,34 @@ def process_recordings_device(chain_sets, audios, ctx=None, chunk=0, rows=False,
                 sides = [Context.side(ctx.device, 400 + p) for p in range(parts)]
                 early = {}
                 taker = run.pieces(chain_sets[0], frames, packets, addrs) if in_pieces else None
+                finish = scanned and rows_packets
+                desc = _scan_desc(chain_sets[0], True, True, True) if finish else None     # (now: recording 0's registers move on with its group)
+                tally = {"rows": 0, "finished": 0, "handed": {}}
+
+                def part_finished(p, lo, hi):
+                    # the packets of finished rows come as rows; a recording with a row that is handed over goes to the codecs from its parts
+                    from concurrent.futures import Future
+                    from .packet_meta import rows_to_packets
+                    entries, prows, handed = run.fetch_packets(lo * nchains, (hi - lo) * nchains, chain_sets[0], sides[p], ("loop-sliced", p), chain_ids, desc)
+                    for rec in range(lo, hi):
+                        k = (rec - lo) * nchains
+                        if k in handed:
+                            early[rec] = (_pool().submit(_host_rows_scanned, chain_sets[rec], handed[k], chain_ids, True, True, True) if rows else
+                                          _pool().submit(_host_stages_scanned, chain_sets[rec], handed[k], True, True, True))
+                            continue
+                        views = []
+                        for c, ch in enumerate(chain_sets[rec]):
+                            e = entries[k + c]
+                            ch[3].shift_register = int(e["lfsr_state"])
+                            views.append(prows[int(e["first"]):int(e["first"]) + int(e["packets"])])
+                        early[rec] = Future()
+                        early[rec].set_result(views if rows else [rows_to_packets(v, ch[4].identifier) for ch, v in zip(chain_sets[rec], views)])
+                    with run._copied_lock:
+                        tally["rows"] += len(entries)
+                        tally["finished"] += int((entries["status"] == 0).sum())
+                        for status in entries["status"][entries["status"] != 0].tolist():
+                            name = N.ROWS_PACKETS_STATUS[status]
+                            tally["handed"][name] = tally["handed"].get(name, 0) + 1
 
                 def part_in_pieces(p, lo, hi):
                     # every piece of these rows is decoded, and the carries that it names are seeded again, before the next one is fetched
@@ -836,6 +941,11 @@ def process_recordings_device(chain_sets, audios, ctx=None, chunk=0, rows=False,
                         hi = min(lo + per, cuts[p + 1])
                         if in_pieces:
                             part_in_pieces(p, lo, hi)
+                            if stages is not None:          # (diagnosis only: the slicers' bytes as the old way brings them)
+                                out += run.fetch(lo * nchains, (hi - lo) * nchains, sides[p], tag=("loop-sliced", p))
+                            continue
+                        if finish:
+                            part_finished(p, lo, hi)
                             if stages is not None:          # (diagnosis only: the slicers' bytes as the old way brings them)
                                 out += run.fetch(lo * nchains, (hi - lo) * nchains, sides[p], tag=("loop-sliced", p))
                             continue
@@ -871,6 +981,8 @@ def process_recordings_device(chain_sets, audios, ctx=None, chunk=0, rows=False,
                         stages["pieces"] = {"pieces": in_pieces, "seeds": taker.seeds, "ordinary": taker.ordinary} if in_pieces else False
                     if beside:
                         stages["beside"] = False                 # (chains that the row form of the scan cannot describe: ignored)
+                    if rows_packets:
+                        stages["rows_packets"] = dict(tally, copied_bytes=run.copied) if finish else False
                 if scanned:
                     out = [early[rec].result() for rec in range(r)]
                     if stages is not None:
@@ -943,6 +1055,8 @@ def process_recordings_device(chain_sets, audios, ctx=None, chunk=0, rows=False,
             stages["pieces"] = False                         # (not the fused-slicer route: ignored)
         if beside:
             stages["beside"] = gave_up if gave_up else False
+        if rows_packets:
+            stages["rows_packets"] = False                   # (not the fused-slicer route: ignored)
     out = []
     if rows:
         futs = [early[rec] if rec in early else _pool().submit(_host_rows, chain_sets[rec], sliced[rec * nchains:(rec + 1) * nchains], chain_ids)
