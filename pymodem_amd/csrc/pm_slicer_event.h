@@ -139,8 +139,10 @@ struct SlicerJob {
 };
 constexpr double kEventMinSps = 16.0;   // samples per symbol below which a batch keeps step32a (at most four symbols per word with events)
 
-// One form for a whole batch.  Hand needs lock_rate - 1 exact (the fma form; it is for 0.5 <= lock_rate <= 2) and finite sps, clk0
-// and tp; Event on top of it, where `event` allows it, every job meets pm_event_ok and takes few enough symbols per word for it to pay
+// One form for a whole batch.  Hand needs lock_rate - 1 exact (the fma form; it is for 0.5 <= lock_rate <= 2), lock_rate > 0 and finite
+// sps, clk0 and tp -- lock_rate - 1 is exact for 0.0, -0.5, -1.0 as well, but there fma(c, lock - 1, c) and the reference's c * lock
+// differ in the sign of a zero (lock 0: c * 0.0 is -0.0 for c < 0, the fma's exact zero sum +0.0; lock < 0: the other way round at
+// c = +0.0), and a stream that ends on such a sample hands that sign out in its phase_clock; Event on top of it, where `event` allows it, every job meets pm_event_ok and takes few enough symbols per word for it to pay
 // (a trip costs ~7 samples of step32a; fsk_9600 at 5 samples per symbol ran its walkers twice as long).
 inline SlicerStep pm_slicer_choose(const SlicerJob *jobs, int njobs, bool event)
 {
@@ -148,7 +150,7 @@ inline SlicerStep pm_slicer_choose(const SlicerJob *jobs, int njobs, bool event)
     for (int j = 0; j < njobs; ++j) {
         const SlicerJob &d = jobs[j];
         const volatile double lm1 = d.lock - 1.0;
-        hand = hand && lm1 + 1.0 == d.lock && d.sps - d.sps == 0.0 && d.clk0 - d.clk0 == 0.0 && d.tp - d.tp == 0.0;
+        hand = hand && lm1 + 1.0 == d.lock && d.lock > 0.0 && d.sps - d.sps == 0.0 && d.clk0 - d.clk0 == 0.0 && d.tp - d.tp == 0.0;
         lm0 = lm0 && (uint32_t)pm_event_bits(lm1) == 0;
         ns0 = ns0 && (uint32_t)pm_event_bits(d.sps) == 0;
         event = event && pm_event_ok(d.sps, d.lock, d.tp, d.clk0) && d.sps >= kEventMinSps;

@@ -380,11 +380,12 @@ def test_slicers_continue_across_calls(ctx, kind):
     # output buffers are sized for 2.2x the nominal symbol count; when a stream exceeds that the batch is redone with the hard bound
     import pymodem_amd.slicer as slicer_mod
     s.tune()
+    shipped = slicer_mod._TIGHT_FACTOR
     slicer_mod._TIGHT_FACTOR = 0.001
     try:
         a1, a2 = s.slice(xi[:70000]), s.slice(xi[70000:])
     finally:
-        slicer_mod._TIGHT_FACTOR = 2.2
+        slicer_mod._TIGHT_FACTOR = shipped
     whole = O.BinarySlicer(48000, "1200", {"lock_rate": "0.77"}).slice(xi)
     assert np.array_equal(np.concatenate([a1.data, a2.data]), whole[0]) and np.array_equal(np.concatenate([a1.address, a2.address]), whole[1])
     s.tune()                                   # retuning returns the object to the just-built state

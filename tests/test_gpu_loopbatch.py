@@ -325,7 +325,7 @@ def test_engine_qpsk_modem():
 ])
 def test_sliced_run_equals_run_then_slice_batch(cfg, rate, carriers, chunk, n):
     """pm_lbatch_run_sliced -- the slicers inside the engine, one lane per stream, state carried from chunk to chunk -- against the same
-    engine's bitmaps sliced by pm_slice_batch (itself pinned to the oracle's slicers in tests/test_gpu_slicer.py): bytes, addresses and
+    engine's bitmaps sliced by pm_slice_batch (itself pinned to the oracle's slicers by the slicer tests of tests/test_gpu_kernels.py): bytes, addresses and
     the slicer objects' end states, for binary and quadrature slicers, several chunks and a ragged last word, noise (a crossing
     at nearly every sample) and level steps."""
     sliced_run_vs_slice_batch(cfg, rate, carriers, chunk, n)

@@ -11,6 +11,8 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
+import slicer_ties as T
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _d, _i, _i64, _vp = ctypes.c_double, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
 
@@ -232,9 +234,115 @@ def test_step_form_of_a_batch(model):
 
 
 @pytest.mark.parametrize("sps,lock,clk0", [(40.0, 0.45, 0.0), (40.0, 0.3, 0.0), (5.0, 0.45, 0.0), (40.0, 0.77, math.nan),
-                                           (40.0, 0.77, math.inf), (math.inf, 0.77, 0.0), (math.nan, 0.77, 0.0)])
+                                           (40.0, 0.77, math.inf), (math.inf, 0.77, 0.0), (math.nan, 0.77, 0.0),
+                                           (40.0, 0.0, 0.0), (25.0, -0.0, 0.0), (40.0, -0.5, 0.0), (5.0, -1.0, 0.0), (25.0, -2.0, 3.5)])
 def test_step_form_falls_back_to_the_compare(model, sps, lock, clk0):
-    # lock_rate - 1 not exact (the fma form needs it), a clock or samples per symbol that are not finite: the reference's compare
+    # lock_rate - 1 not exact (the fma form needs it), a clock or samples per symbol that are not finite: the reference's compare.
+    # lock_rate <= 0, although lock_rate - 1 is exact for 0.0, -0.5, -1.0: fma(c, lock - 1, c) and the reference's c * lock agree in value
+    # but not in the sign of a zero (lock 0: c * 0.0 is -0.0 for c < 0, the fma's exact zero sum is +0.0; lock < 0: the other way round at
+    # c = +0.0), and a stream that ends on such a sample carries that sign out in phase_clock
     if lock in (0.45, 0.3):
         assert (lock - 1.0) + 1.0 != lock
+    if lock <= 0.0:
+        assert (lock - 1.0) + 1.0 == lock
     assert choose(model, [(sps, lock, clk0)]) == (COMPARE, False, False)
+    assert choose(model, [(40.0, 0.75, 0.0), (sps, lock, clk0)]) == (COMPARE, False, False)
+    assert choose(model, [(sps, lock, clk0)], event=False) == (COMPARE, False, False)
+
+
+# ---- the inputs of the tie tests (tests/slicer_ties.py; the GPU tests that use them: test_gpu_slicer_ties.py, test_gpu_rowslice_ties.py) -----
+_FORM_NAMES = {COMPARE: T.COMPARE, HAND: T.HAND, EVENT: T.EVENT}
+
+
+def header_choice(model, jobs, event=True):
+    form, lm0, ns0 = choose(model, jobs, event)
+    return _FORM_NAMES[form], int(lm0), int(ns0)
+
+
+def test_python_copy_of_the_form_choice_equals_the_header(model):
+    for thr in [12.0, 1.0, 2.0, 7.5, math.inf, math.nan] + [sps / 2.0 - 0.5 for sps, _ in PAIRS + T.NATURAL_PAIRS]:
+        assert bits_equal(T.symbol_clock_threshold(thr), model.model_threshold(thr)) or (math.isnan(T.symbol_clock_threshold(thr))
+                                                                                         and math.isnan(model.model_threshold(thr))), thr
+    assert math.isnan(T.symbol_clock_threshold(1.0))          # 3 samples per symbol: the header cannot pin tp down, the batch compares
+    singles = [(sps, lock, 0.0) for sps, lock in T.NATURAL_PAIRS] + [(sps, lock, 0.0) for sps, lock, _ in T.INJECTED_CONFIGS]
+    singles += [(sps, lock, clk) for sps, lock, _ in T.INJECTED_CONFIGS for clk in T.injected_clocks(sps) + [T.OUT_OF_RANGE]]
+    singles += [(sps, lock, clk0) for sps, lock in PAIRS for clk0 in (0.0, 3000.0)] + [(40.0, math.nan, 0.0), (40.0, 0.77, math.inf)]
+    for job in singles:
+        for event in (True, False):
+            assert T.choose([job], event) == header_choice(model, [job], event), (job, event)
+    for sps, lock, _ in T.INJECTED_CONFIGS:
+        batch = [(sps, lock, clk) for clk in T.injected_clocks(sps)]
+        for jobs in (batch, batch + [(sps, lock, T.OUT_OF_RANGE)]):
+            for event in (True, False):
+                assert T.choose(jobs, event) == header_choice(model, jobs, event), (sps, lock, event)
+
+
+def bits_equal(a, b):
+    return T.bits_of(a) == T.bits_of(b)
+
+
+def test_tie_test_parameters_reach_every_kernel(model):
+    # the nine walker kernels: Compare, and Hand and Event with LM0 x NS0 each
+    got = [header_choice(model, [(sps, lock, 0.0)], event=not no_event) for sps, lock, no_event in T.NINE]
+    assert got == T.NINE_FORMS and len(set(got)) == 9
+    # ... each still the same kernel from every injected clock in pm_event_ok's range, and step32a from the one beyond it
+    for (sps, lock, no_event), form in zip(T.NINE, T.NINE_FORMS):
+        jobs = [(sps, lock, clk) for clk in T.injected_clocks(sps)]
+        assert header_choice(model, jobs, event=not no_event) == form
+        beyond = header_choice(model, jobs + [(sps, lock, T.OUT_OF_RANGE)], event=not no_event)
+        assert beyond == ((T.HAND,) + form[1:] if form[0] == T.EVENT else form)
+    # the five row kernels (the row slicers are chosen without the event step, from a clock of 0.0)
+    rows = [header_choice(model, [(48000.0 / rate, lock, 0.0)] * 2, event=False) for rate, lock in T.ROW_CASES]
+    assert rows == T.ROW_FORMS and len(set(rows)) == 5
+    assert 48000.0 / 1920.0 == 25.0 and 48000.0 / 1800.0 == T.NS0_OFF
+
+
+@pytest.mark.parametrize("sps,lock", T.NATURAL_PAIRS)
+def test_natural_tie_inputs_hold_their_ties(sps, lock):
+    assert T.check_natural_preconditions(sps, lock)
+    for name, n, cut in T.natural_plan(sps, lock):
+        if cut is not None:                                  # the cut leaves the tie as the last sample of a partial last word
+            x = T.natural_streams(sps, n)[name]
+            ties = T.reference(x[:cut] < 0, sps, lock)[0]
+            assert ties and ties[-1] == cut - 1 and cut % 64 != 0 and cut < n, (name, n, cut)
+
+
+def test_injected_clocks_decide_at_the_first_sample():
+    # tp takes a symbol at sample 0 and ties there when thr is an integer; its predecessor does not; tp - 1 ties a sample later
+    for sps, lock, _ in T.INJECTED_CONFIGS:
+        thr = sps / 2.0 - 0.5
+        tp = T.symbol_clock_threshold(thr)
+        quiet = np.zeros(3) < 0
+        assert T.reference(quiet, sps, lock, clk0=tp)[1][:1] == [0]
+        assert 0 not in T.reference(quiet, sps, lock, clk0=math.nextafter(tp, -math.inf))[1]
+        assert T.reference(quiet, sps, lock, clk0=math.nextafter(tp, math.inf))[1][:1] == [0]
+        if thr == int(thr):
+            assert T.reference(quiet, sps, lock, clk0=tp)[0][:1] == [0] and T.reference(quiet, sps, lock, clk0=tp - 1.0)[0][:1] == [1]
+        assert (len(T.injected_clocks(sps)) + 1) * len(T.injected_streams(64, sps, 0)) <= 64
+
+
+TIE_SPS, TIE_LOCKS = [17.0, 25.0, 33.0], [0.5, 0.75, 0.875, 1.0]
+
+
+@pytest.mark.parametrize("lock", TIE_LOCKS)
+@pytest.mark.parametrize("sps", TIE_SPS)
+def test_event_step_equals_reference_on_tie_streams(model, sps, lock):
+    """Odd integer samples per symbol (an integer threshold): silence ties at every symbol, and with lock_rate 0.5 frames tie between
+    crossings.  The event header against the reference recurrence on silence, frames and a lone crossing on and behind a tie, from the
+    clocks at and around tp as well."""
+    n = 25600
+    ties, syms, _ = T.reference(T.silence(n) < 0, sps, lock)
+    assert ties == syms and len(ties) >= n / sps - 1
+    streams = T.natural_streams(sps, n)
+    assert set(streams) == {"silence", "frames", "cross-on-tie", "cross-after-tie"}
+    if lock == 0.5:
+        x = streams["frames"]
+        assert any(t > int(np.argmax(x < 0)) for t in T.reference(x < 0, sps, lock)[0])
+    on, after = (int(np.argmax(streams[k] < 0)) for k in ("cross-on-tie", "cross-after-tie"))
+    assert on in ties and after - 1 in ties
+    for name, x in streams.items():
+        zc = crossings(np.where(x < 0, -1, 1))
+        compare(model, zc, sps, lock)
+        for clk0 in T.injected_clocks(sps):
+            compare(model, zc[:8], sps, lock, clk0=clk0)
+        compare(model, zc, sps, lock, evt=0)                  # every word through step32a's operations
