@@ -720,6 +720,45 @@ typedef struct pm_rows_packets_entry {
 int pm_rows_packets(pm_ctx *ctx, const pm_rowslice_rec *d_recs, const uint16_t *d_steps, int64_t cap, int64_t row0, int nrows,
                     const pm_rows_scan_chain *h_chains, int nchains, const int32_t *h_sources, const int64_t *h_counts, const void *d_block,
                     const int64_t *h_offsets, void *d_out, size_t out_bytes, size_t *h_used);
+/* FINISHED STREAMS: the same last step for the job form.  The packets of the jobs of a pm_stream_scan call, made on the device from the block
+ * that the call has just written -- for every job exactly the packets that pm_codec_fetch hands out for a just-created codec that is fed the
+ * job's stream (pm_codec_decode), wherever the job's frame table (AX.25) or packet table (IL2P) says everything about the stream.  The rules
+ * are pm_rows_packets' (pm_rows_packets.h), and so are the statuses.  Enqueued on the ctx stream behind that pm_stream_scan; h_jobs, njobs,
+ * d_block and h_offsets are its arguments and results, unchanged.  A job of kind 0 must have been scanned with frames, one of kind 1 with
+ * packets, and either needs d_addr, the stream's n int64 addresses on the device (pm_slice_job.d_addr): a packet's address is read there,
+ * whole -- no checkpoints, no 16-bit steps, so `addrs` is not needed and an address step of any size is no obstacle.  A job with d_carry is
+ * refused (the tables of a piece say nothing about the packets that began in front of it).  All of these PM_ERR_ARG, nothing enqueued.
+ * h_sources[j]: what goes into source_decoder for job j, NULL: j.  d_block must be DEVICE memory, as for pm_rows_packets: the launches read it.
+ * d_out (8-byte aligned, out_bytes) receives the DENSE form:
+ *     pm_stream_packets_head               32 bytes: the jobs of the call, how many of them are not FINISHED, the records and their bytes
+ *     pm_stream_packets_entry[njobs]       32 bytes a job: the LFSR register behind the stream, the status, the job's records, where the
+ *                                          first of them begins (counted from the first record of the call), corrected_left as above
+ *     the records                          job after job, in stream order within a job: the 40-byte pm_packet_head, `len` data bytes, zeros
+ *                                          up to a multiple of 8
+ * This is NOT pm_packets_pack's wire form, which is unpadded: here every record begins at a multiple of 8.  A frame longer than PM_PKT_MAX
+ * is cut as in a pm_packet.  The statuses are PM_ROWS_PACKETS_*; LEFT_OUT does not occur.  The room for records is what out_bytes leaves
+ * behind the entries: the first job whose records would pass it takes none and is NO_ROOM, and so is every job behind it; their first_byte
+ * is head.bytes.  *h_used = the bytes of head and entries (PM_ERR_CAPACITY, with it set, when out_bytes is less).
+ * d_out is only ever WRITTEN, in whole aligned words of 8 bytes: it may be page-locked host memory that the device reaches.  What a later
+ * launch reads of an earlier one's results -- the accepted lists, the record offsets, the entries -- stays in context scratch.
+ * Three launches.  Walk: a wave a job; AX.25 -- the lanes take the listed events 64 per trip, each lane makes the rule's checks for its own
+ * event, a ballot and a count of the lanes in front give the places in the accepted list, a prefix sum over the wave the record offsets, both
+ * carried from trip to trip; IL2P -- one lane walks the packet table by the rule, whose register makes it sequential.  Room: one wave scans
+ * the jobs' bytes and writes head and entries.  Build: a fixed grid of waves, wave w the records w, w + waves, ... */
+typedef struct pm_stream_packets_head {
+    int32_t jobs, handed;
+    int64_t packets;
+    int64_t bytes;
+    int64_t reserved;
+} pm_stream_packets_head;
+typedef struct pm_stream_packets_entry {
+    uint64_t lfsr_state;
+    int32_t status, packets;
+    int64_t first_byte;
+    int32_t corrected_left, reserved;
+} pm_stream_packets_entry;
+int pm_stream_packets(pm_ctx *ctx, const pm_scan_job *h_jobs, int njobs, const int32_t *h_sources, const void *d_block, const int64_t *h_offsets,
+                      void *d_out, size_t out_bytes, size_t *h_used);
 /* MARKS:a sliced run that says, chunk by chunk, how far every row has got -- what pm_rows_scan_pieces' d_upto is shaped for, so that the
  * rows of a run can be taken and decoded BESIDE the run instead of behind it.  A pm_lbatch_marks object (made for one engine and up to
  * max_chunks chunks; destroy it before the engine) holds for each chunk t of a run:
@@ -1025,6 +1064,17 @@ int pm_pipe_slots(pm_pipe *pipe);                        /* recordings between d
 int pm_pipe_release(pm_pipe *pipe, int64_t ticket);      /* the result's memory */
 int pm_pipe_drain(pm_pipe *pipe);                        /* every recording submitted so far is through */
 int pm_pipe_stats(pm_pipe *pipe, int64_t *h_batches, int64_t *h_batch_recordings, double *h_slice_busy_ms, double *h_host_busy_ms);
+/* FINISHED CHAINS: a pipeline made on a context with the switch pipe_done (PM_PIPE_DONE, default 0; implies pipe_scan, pipe_frames and
+ * pipe_packets) keeps its scan parts in a device block of the slicer worker's and has pm_stream_packets finish every group of 64 scan
+ * jobs into the batch's host block, behind the compact forms.  A chain whose entry is FINISHED gets no codec: its records are copied into the
+ * recording's rows between those that the codecs of the other chains deliver; every other chain is decoded from the compact bytes, the
+ * unscanned way.  Results are those of the pipeline without the switch, field for field.  The room of a group is the sum over its jobs of
+ * what a stream of n bytes can hold at the most -- AX.25: n / 19 + 2 records of 40 + pad8(len) <= len + 48 bytes with frames that do not
+ * overlap, pad8(n) + 48 (n / 19 + 2); IL2P: n / 64 + 2 records of at most 72 bytes and a payload each, payloads that do not overlap,
+ * pad8(n) + 72 (n / 64 + 2) -- so NO_ROOM does not occur, unless pipe_done_room (PM_PIPE_DONE_ROOM, bytes of records per group) says less.
+ * pm_pipe_done_stats: the chains since creation that were FINISHED on the device, those handed over, and the latter by status
+ * (h_status_counts[12], indexed by PM_ROWS_PACKETS_*; entry 0 stays 0).  All zero for a pipeline without the switch.  Any pointer may be NULL. */
+int pm_pipe_done_stats(pm_pipe *pipe, int64_t *h_finished, int64_t *h_handed, int64_t *h_status_counts);
 pm_ctx *pm_pipe_side_ctx(pm_pipe *pipe, int worker);     /* a slicer worker's context (NULL past the last): for pm_prof_* */
 pm_ctx *pm_pipe_demod_ctx(pm_pipe *pipe, int k);         /* demod stream k (NULL past the last); the pipeline's own, except stream 0 under pipe_queue_plan 0: the caller's context */
 int pm_pipe_destroy(pm_pipe *pipe);                      /* drains first */

@@ -220,6 +220,57 @@ def rows_packets_bytes(nrows, packets=0):
     return ROWS_PACKETS_HEAD_BYTES + ROWS_PACKETS_ENTRY_BYTES * nrows + ctypes.sizeof(Packet) * packets
 
 
+class StreamPacketsHead(ctypes.Structure):
+    """pm_stream_packets_head"""
+    _fields_ = [("jobs", ctypes.c_int32), ("handed", ctypes.c_int32), ("packets", ctypes.c_int64), ("bytes", ctypes.c_int64), ("reserved", ctypes.c_int64)]
+
+
+class StreamPacketsEntry(ctypes.Structure):
+    """pm_stream_packets_entry"""
+    _fields_ = [("lfsr_state", ctypes.c_uint64), ("status", ctypes.c_int32), ("packets", ctypes.c_int32), ("first_byte", ctypes.c_int64),
+                ("corrected_left", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+STREAM_PACKETS_HEAD_BYTES, STREAM_PACKETS_ENTRY_BYTES = 32, 32
+
+
+def stream_packets_head_dtype():
+    """NumPy view of pm_stream_packets_head: what pm_stream_packets' d_out begins with."""
+    import numpy as np
+    return np.dtype([("jobs", "<i4"), ("handed", "<i4"), ("packets", "<i8"), ("bytes", "<i8"), ("reserved", "<i8")])
+
+
+def stream_packets_entry_dtype():
+    """NumPy view of pm_stream_packets_entry: a job of pm_stream_packets' d_out (the statuses are ROWS_PACKETS_STATUS)."""
+    import numpy as np
+    return np.dtype([("lfsr_state", "<u8"), ("status", "<i4"), ("packets", "<i4"), ("first_byte", "<i8"), ("corrected_left", "<i4"), ("reserved", "<i4")])
+
+
+def stream_packets_bytes(njobs, record_bytes=0):
+    """out_bytes of pm_stream_packets for njobs jobs and room for `record_bytes` bytes of records."""
+    return STREAM_PACKETS_HEAD_BYTES + STREAM_PACKETS_ENTRY_BYTES * njobs + record_bytes
+
+
+def stream_packets_record_bytes(length):
+    """A record of the dense form: the 40-byte head, the packet's bytes (PKT_MAX at the most), zeros up to a multiple of 8."""
+    return 40 + (min(length, PKT_MAX) + 7) // 8 * 8
+
+
+def stream_packets_records(raw, njobs):
+    """The records of pm_stream_packets' dense form in `raw` (d_out as uint8, downloaded): yields (job, head, data) record by record, job
+    after job -- head a head_dtype() scalar, data the packet's `len` bytes (views of raw)."""
+    import numpy as np
+    raw = np.asarray(raw, dtype=np.uint8)
+    entries = raw[STREAM_PACKETS_HEAD_BYTES:stream_packets_bytes(njobs)].view(stream_packets_entry_dtype())
+    base = stream_packets_bytes(njobs)
+    for job in range(njobs):
+        at = base + int(entries["first_byte"][job])
+        for _ in range(int(entries["packets"][job])):
+            head = raw[at:at + 40].view(head_dtype())[0]
+            yield job, head, raw[at + 40:at + 40 + int(head["len"])]
+            at += stream_packets_record_bytes(int(head["len"]))
+
+
 def scan_packet_dtype():
     """NumPy view of a place of the packet table."""
     import numpy as np
@@ -394,6 +445,8 @@ _SIGS = {
                      ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_size_t)], _int),
     "pm_rows_packets": ([_vp, _vp, _vp, _i64, _i64, _int, ctypes.POINTER(RowsScanChain), _int, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(_i64), _vp,
                          ctypes.POINTER(_i64), _vp, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)], _int),
+    "pm_stream_packets": ([_vp, ctypes.POINTER(ScanJob), _int, ctypes.POINTER(ctypes.c_int32), _vp, ctypes.POINTER(_i64), _vp, ctypes.c_size_t,
+                           ctypes.POINTER(ctypes.c_size_t)], _int),
     "pm_rows_carry_start": ([_vp, _vp, _i64, _int, ctypes.POINTER(RowsScanChain), _int], _int),
     "pm_rows_scan_pieces": ([_vp, _vp, _vp, _vp, _i64, _i64, _int, ctypes.POINTER(RowsScanChain), _int, _vp, _vp, ctypes.c_int32, ctypes.POINTER(_i64), _vp,
                             ctypes.c_size_t, ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_size_t)], _int),
@@ -422,6 +475,7 @@ _SIGS = {
     "pm_pipe_slots": ([_vp], _int),
     "pm_pipe_drain": ([_vp], _int),
     "pm_pipe_stats": ([_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)], _int),
+    "pm_pipe_done_stats": ([_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64), ctypes.POINTER(_i64)], _int),
     "pm_pipe_side_ctx": ([_vp, _int], _vp),
     "pm_pipe_demod_ctx": ([_vp, _int], _vp),
     "pm_pipe_destroy": ([_vp], _int),

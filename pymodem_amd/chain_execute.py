@@ -953,7 +953,7 @@ class NativePipeline:
     raises ValueError for anything else (use RecordingPipeline there)."""
 
     def __init__(self, chains, max_samples, address_distance, ctx=None, names=None, chain_ids=None, slots=0, slice_workers=0, slice_group=0,
-                 host_threads=0, decode_threads=0, slice_min_group=0, demod_streams=0, keep_slices=False, scan=False, frames=False, packets=False, addrs=False):
+                 host_threads=0, decode_threads=0, slice_min_group=0, demod_streams=0, keep_slices=False, scan=False, frames=False, packets=False, addrs=False, done=False):
         import os
         demod_streams = demod_streams or int(os.environ.get("PYMODEM_AMD_PIPE_DEMOD_STREAMS", 0))
         slots = slots or int(os.environ.get("PYMODEM_AMD_PIPE_SLOTS", 0))              # tuning knobs (DESIGN.md 4.4b)
@@ -1034,7 +1034,9 @@ class NativePipeline:
         # reads the switch from its context.  frames: that, and the AX.25 chains' frames (de-stuffed bytes and CRC) come from the device too.
         # packets: that, and the IL2P chains' attempts (headers and RS blocks) are made on the device too
         # addrs: that, and every scan job writes address checkpoints from which the host stage resolves the few addresses it needs
-        on = {k: 1 for k, v in (("pipe_scan", scan), ("pipe_frames", frames), ("pipe_packets", packets), ("pipe_addrs", addrs)) if v}
+        # done: frames and packets, and every chain whose table says everything about its stream is finished on the device (pm_stream_packets
+        # behind pm_stream_scan): the host stage copies its records and makes no codec for it (done_stats() says how many went that way)
+        on = {k: 1 for k, v in (("pipe_scan", scan), ("pipe_frames", frames), ("pipe_packets", packets), ("pipe_addrs", addrs), ("pipe_done", done)) if v}
         ctx.tune(**on)
         try:
             check(lib().pm_pipe_create(ctx.handle, ctypes.byref(desc), ctypes.byref(h)))
@@ -1046,6 +1048,14 @@ class NativePipeline:
         self.nchains = n
         self.done_at_ms = {}                                # ticket -> when it left the last stage (host clock since the pipeline was made)
         self.slots = int(lib().pm_pipe_slots(h))            # as pm_pipe_create settled it
+
+    def done_stats(self):
+        """pm_pipe_done_stats: {"finished": chains finished on the device since the pipeline was made, "handed": chains handed over to the
+        codecs, "status": {name: count} of the latter by PM_ROWS_PACKETS_* status}.  All zero without `done`."""
+        from ._native import ROWS_PACKETS_STATUS
+        fin, handed, counts = ctypes.c_int64(), ctypes.c_int64(), (ctypes.c_int64 * 12)()
+        check(lib().pm_pipe_done_stats(self._h, ctypes.byref(fin), ctypes.byref(handed), counts))
+        return {"finished": fin.value, "handed": handed.value, "status": {ROWS_PACKETS_STATUS[k]: int(counts[k]) for k in range(12) if counts[k]}}
 
     def prefetch(self, host_audio):
         """Start copying a recording (host int16 array) into HBM on a copy stream; returns a handle for submit().  Called one

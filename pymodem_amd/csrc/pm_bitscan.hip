@@ -33,6 +33,10 @@
 // pm_rows_packets, behind pm_rows_scan on the same stream, READS a block in device memory: a lane a row walks the row's frame table or packet
 // table by the rules of pm_rows_packets.h, one workgroup gives the accepted packets their places, and a fixed grid of waves builds the
 // pm_packet rows that pm_codec_fetch would hand out; a row whose table does not say everything about it is named with the reason.
+// pm_stream_packets is the same last step for the jobs of a pm_stream_scan call, into a dense form that may lie in page-locked host memory:
+// a wave a job walks the table (AX.25: the lanes take the listed events 64 per trip, places from a ballot, record offsets from a prefix sum
+// over the wave), one wave gives the jobs their room, and the build launch is the row form's, a template on where a part lies, where an
+// address comes from and what the output looks like.
 #include "pm_common.h"
 #include "pm_bitscan_addrs.h"
 #include "pm_bitscan_events.h"
@@ -1100,37 +1104,42 @@ __global__ __launch_bounds__(kLanes) void rows_packets_room_kernel(int nrows, pm
     if (t == 0) *head = pm_rows_packets_head{nrows, handed, (int64_t)kept};
 }
 
-// Launch 3: a fixed grid, a wave a workgroup; wave w takes the packets w, w + waves, ... up to the head's total.  The packet's row by binary
+// Launch 3: a fixed grid, a wave a workgroup; wave w takes the packets w, w + waves, ... up to the call's total.  The packet's row by binary
 // search over `first`; its bytes put together in LDS -- IL2P: the AX.25 header that lane 0 rebuilds from the 13 bytes in the area, the
 // payload a byte a lane, the CRC of both by the frames launch's join, the carried CRC from the Hamming-coded bytes behind the last block
-// or the computed one; AX.25: the frame from the area, its CRC from the table -- the address from the checkpoint in front and up to 63
-// steps, a lane a step; then the row's 1280 data bytes as whole words, zeros behind the packet, and its 40-byte head by lane 0
-// (pm_rpk::packet_build says the same for one thread).
-__global__ __launch_bounds__(64) void rows_packets_build_kernel(RowPk K, const uint8_t *block, uint8_t *out, const RowPkInfo *info, const pm_rpk::Accepted *acc)
+// or the computed one; AX.25: the frame from the area, its CRC from the table -- then the address, the data bytes as whole words with zeros
+// behind the packet, and the 40-byte head by lane 0 (pm_rpk::packet_build_to says the same for one thread).
+// What differs between the row form and the job form is the source S: which row (or job) a packet belongs to and where that one's part
+// lies, where the address of a byte comes from, and where the packet goes and how many words of data it takes there.
+struct BuildItem {
+    pm_rpk::Part p;
+    pm_rpk::Accepted a;
+    int kind, crc, source;
+    uint8_t *dst;
+};
+template <class Src>
+__device__ inline void packets_build(const Src &S, const uint8_t *block)
 {
     using namespace pm_rpk;
     __shared__ uint64_t pkt64[PM_PKT_MAX / 8];
     __shared__ uint16_t crc_table[256];
     const int lane = (int)threadIdx.x;
     uint8_t *pkt = reinterpret_cast<uint8_t *>(pkt64);
-    const pm_rows_packets_entry *entries = reinterpret_cast<const pm_rows_packets_entry *>(out + kHeadBytes);
-    uint8_t *rows = out + kHeadBytes + (size_t)kEntryBytes * (size_t)K.nrows;
-    const int64_t total = reinterpret_cast<const pm_rows_packets_head *>(out)->packets;
+    const int64_t total = S.total();
     if ((int64_t)blockIdx.x >= total) return;
     wave_crc_table(crc_table, lane);
     for (int64_t q = (int64_t)blockIdx.x; q < total; q += (int64_t)gridDim.x) {
-        const int r = row_of_packet([entries](int i) { return entries[i].first; }, K.nrows, q);
-        const RowPkInfo ri = info[r];
-        const int c = (int)((K.row0 + r) % K.nchains), kind = K.kind[c];
-        const Accepted a = acc[ri.acc0 + (q - entries[r].first)];
-        const Part p = part_of(block + ri.scan, kind, ri.n);
+        const int r = S.row_of(q);
+        const BuildItem it = S.item(block, r, q);
+        const Part &p = it.p;
+        const Accepted &a = it.a;
         __syncthreads();
         for (int v = lane; v < PM_PKT_MAX / 8; v += 64) pkt64[v] = 0;
         __syncthreads();
         int len, calculated;
         uint32_t carried;
         int64_t k;
-        if (kind == 1) {
+        if (it.kind == 1) {
             const pm_il2p::Rec rec = ld_rec(p, (int32_t)a.index);
             const uint8_t *src = p.area + rec.off;
             int hl = 0;
@@ -1145,7 +1154,7 @@ __global__ __launch_bounds__(64) void rows_packets_build_kernel(RowPk K, const u
             calculated = (int)((crc ^ 0xFFFF) & 0xFFFF);
             int64_t E = (int64_t)a.bit + 1;
             carried = (uint32_t)calculated;                 // il2p.py:427-431: without the trailing CRC the computed one is appended
-            if (K.pkopt[c] & 1) {
+            if (it.crc) {
                 carried = (uint32_t)pm_il2p::hamming_crc(byte_at(p.plain, E), byte_at(p.plain, E + 8), byte_at(p.plain, E + 16), byte_at(p.plain, E + 24));
                 E += 32;
             }
@@ -1166,18 +1175,204 @@ __global__ __launch_bounds__(64) void rows_packets_build_kernel(RowPk K, const u
             k = (int64_t)(a.bit >> 3);
         }
         __syncthreads();
-        // pm_addrs::resolve across the wave: steps (k & ~63) + 1 .. k
+        const int64_t addr = S.address(p, r, k, lane);
+        for (int v = lane, words = S.data_words(len); v < words; v += 64) reinterpret_cast<uint64_t *>(it.dst + 40)[v] = pkt64[v];
+        if (lane == 0) {
+            const HeadWords h = head_words(addr, pkt, len, a.corrected, calculated, carried, it.source);
+            for (int v = 0; v < 5; ++v) reinterpret_cast<uint64_t *>(it.dst)[v] = h.w[v];
+        }
+    }
+}
+
+// the row form: head and entries are read where the room launch left them, in d_out; a packet is a whole pm_packet row; the address is the
+// checkpoint in front plus up to 63 of the row's steps, a lane a step (pm_addrs::resolve across the wave: steps (k & ~63) + 1 .. k)
+struct RowBuild {
+    const RowPk &K;
+    uint8_t *out;
+    const RowPkInfo *info;
+    const pm_rpk::Accepted *acc;
+    __device__ const pm_rows_packets_entry *entries() const { return reinterpret_cast<const pm_rows_packets_entry *>(out + pm_rpk::kHeadBytes); }
+    __device__ int64_t total() const { return reinterpret_cast<const pm_rows_packets_head *>(out)->packets; }
+    __device__ int row_of(int64_t q) const
+    {
+        const pm_rows_packets_entry *e = entries();
+        return pm_rpk::row_of_packet([e](int i) { return e[i].first; }, K.nrows, q);
+    }
+    __device__ BuildItem item(const uint8_t *block, int r, int64_t q) const
+    {
+        const RowPkInfo ri = info[r];
+        const int c = (int)((K.row0 + r) % K.nchains), kind = K.kind[c];
+        uint8_t *rows = out + pm_rpk::kHeadBytes + (size_t)pm_rpk::kEntryBytes * (size_t)K.nrows;
+        return BuildItem{pm_rpk::part_of(block + ri.scan, kind, ri.n), acc[ri.acc0 + (q - entries()[r].first)], kind, K.pkopt[c] & 1, K.source[c],
+                         rows + (size_t)q * sizeof(pm_packet)};
+    }
+    __device__ int64_t address(const pm_rpk::Part &p, int r, int64_t k, int lane) const
+    {
         const uint16_t *steps = K.steps + (K.row0 + r) * K.cap;
         const int64_t i = (k & ~(int64_t)63) + 1 + lane;
         uint32_t gone = i <= k ? steps[i] : 0u;
         for (int dl = 32; dl; dl >>= 1) gone += __shfl_xor(gone, dl);
-        uint8_t *dst = rows + (size_t)q * sizeof(pm_packet);
-        for (int v = lane; v < PM_PKT_MAX / 8; v += 64) reinterpret_cast<uint64_t *>(dst + 40)[v] = pkt64[v];
-        if (lane == 0) {
-            const HeadWords h = head_words(p.addrs[k >> 6] + (int64_t)gone, pkt, len, a.corrected, calculated, carried, K.source[c]);
-            for (int v = 0; v < 5; ++v) reinterpret_cast<uint64_t *>(dst)[v] = h.w[v];
-        }
+        return p.addrs[k >> 6] + (int64_t)gone;
     }
+    __device__ static int data_words(int) { return PM_PKT_MAX / 8; }
+};
+__global__ __launch_bounds__(64) void rows_packets_build_kernel(RowPk K, const uint8_t *block, uint8_t *out, const RowPkInfo *info, const pm_rpk::Accepted *acc)
+{
+    packets_build(RowBuild{K, out, info, acc}, block);
+}
+
+// ---- pm_stream_packets: the same last step for the jobs of a pm_stream_scan call, into the dense form (the rules: pm_rows_packets.h) ---------
+// What the three launches know of the call, by value: where a job's part lies (the host's offsets), its bytes, its addresses.
+struct StreamPk {
+    int64_t off[kScanJobs];
+    const int64_t *addr[kScanJobs];
+    int32_t n[kScanJobs];
+    int32_t acc0[kScanJobs];                // the job's first place in the accepted list and the record offsets
+    int32_t source[kScanJobs];
+    int8_t kind[kScanJobs], tol[kScanJobs];
+    uint8_t crc[kScanJobs];
+    int32_t njobs;
+};
+static_assert(sizeof(StreamPk) + 64 <= 4096, "the table goes to the kernels by value");
+// What the launches leave for each other, in context scratch (d_out is never read).  entry[j].first_byte: behind the walk launch the bytes
+// of job j's records, behind the room launch where they begin.
+struct StreamPkNotes {
+    pm_stream_packets_entry entry[kScanJobs];
+    int64_t first[kScanJobs];               // the job's first record among the call's
+    int64_t packets, bytes;                 // the records that have room, and their bytes
+};
+__device__ inline int64_t wave_incl_sum(int64_t v, int lane)
+{
+    for (int dl = 1; dl < 64; dl <<= 1) {
+        const int64_t o = __shfl_up(v, dl);
+        if (lane >= dl) v += o;
+    }
+    return v;
+}
+
+// Launch 1: a wave a job.  AX.25: trips of 64 listed events, a lane an event -- the rule's checks for that event, the lane's place in the
+// accepted list from a ballot and the count of the lanes in front, its record's offset from a prefix sum of the record sizes over the wave,
+// both on top of what the trips before counted.  A table that cannot be the stream's ends the walk at the trip that finds it (what the
+// trips before listed is never looked at: the job has no packets).  IL2P: lane 0 walks the packet table by the rule.
+__global__ __launch_bounds__(64) void stream_packets_walk_kernel(StreamPk K, const uint8_t *block, StreamPkNotes *notes, pm_rpk::Accepted *acc, int64_t *recoff)
+{
+    using namespace pm_rpk;
+    const int j = (int)blockIdx.x, lane = (int)threadIdx.x, kind = K.kind[j];
+    const Part p = part_of(block + K.off[j], kind, K.n[j]);
+    Accepted *mine = acc + K.acc0[j];
+    int64_t *offs = recoff + K.acc0[j];
+    pm_stream_packets_entry out{ld64(p.rec), PM_ROWS_PACKETS_NO_CODEC, 0, 0, 0, 0};
+    int64_t bytes = 0;
+    if (kind == 0) {
+        int32_t events, count = 0;
+        out.status = ax25_start(p, &events);
+        for (int32_t e0 = 0; e0 < events; e0 += 64) {
+            const int32_t e = e0 + lane;
+            Ax25Event ev{false, false, 0, 0};
+            if (e < events) ev = ax25_event(p, e);
+            if (__any(ev.bad)) {
+                out.status = PM_ROWS_PACKETS_LONG_FRAME;
+                break;
+            }
+            const uint64_t taken = __ballot(ev.take);
+            const int64_t size = ev.take ? record_bytes(ev.len) : 0, incl = wave_incl_sum(size, lane);
+            if (ev.take) {
+                const int place = count + lanes_before(taken, lane);
+                mine[place] = Accepted{(uint32_t)e, ev.P, 0, 0};
+                offs[place] = bytes + incl - size;
+            }
+            count += __popcll(taken);
+            bytes += __shfl(incl, 63);
+        }
+        out.packets = count;
+    } else if (kind == 1 && lane == 0) {
+        const Part &pp = p;
+        int64_t *sum = &bytes;
+        out.status = il2p_walk(p, K.tol[j], K.crc[j] != 0, &out.packets, &out.corrected_left, [mine, offs, sum, &pp](int i, const Accepted &a) {
+            mine[i] = a;
+            offs[i] = *sum;
+            *sum += record_bytes(il2p_len(pp, ld_rec(pp, (int32_t)a.index)));
+        });
+    }
+    if (lane == 0) {
+        if (out.status != PM_ROWS_PACKETS_FINISHED) {
+            out.packets = out.corrected_left = 0;
+            bytes = 0;
+        }
+        out.first_byte = bytes;
+        notes->entry[j] = out;
+    }
+}
+
+// Launch 2: one wave, a lane a job: an inclusive scan of the jobs' bytes and of their counts.  A job whose records would pass the room takes
+// none, and no job behind it does (the sum only grows): NO_ROOM, at the total.  Head and entries go out as whole words.
+__global__ __launch_bounds__(64) void stream_packets_room_kernel(int njobs, StreamPkNotes *notes, uint64_t *out, int64_t capacity)
+{
+    const int j = (int)threadIdx.x;
+    const bool active = j < njobs;
+    pm_stream_packets_entry e{0, 0, 0, 0, 0, 0};
+    if (active) e = notes->entry[j];
+    const int64_t bytes = e.first_byte, incl_b = wave_incl_sum(bytes, j), incl_p = wave_incl_sum((int64_t)e.packets, j);
+    const bool over = pm_rpk::no_room(incl_b, capacity);
+    int64_t kept_b = active && !over ? incl_b : 0, kept_p = active && !over ? incl_p : 0;
+    for (int dl = 32; dl; dl >>= 1) {
+        kept_b = max(kept_b, (int64_t)__shfl_xor(kept_b, dl));
+        kept_p = max(kept_p, (int64_t)__shfl_xor(kept_p, dl));
+    }
+    const int handed = __popcll(__ballot(active && (over || e.status != PM_ROWS_PACKETS_FINISHED)));
+    if (active) {
+        e.first_byte = over ? kept_b : incl_b - bytes;
+        if (over) {
+            e.status = PM_ROWS_PACKETS_NO_ROOM;
+            e.packets = e.corrected_left = 0;
+        }
+        notes->entry[j] = e;
+        notes->first[j] = over ? kept_p : incl_p - e.packets;
+        uint64_t *w = out + 4 + 4 * j;
+        w[0] = e.lfsr_state;
+        w[1] = (uint64_t)(uint32_t)e.status | (uint64_t)(uint32_t)e.packets << 32;
+        w[2] = (uint64_t)e.first_byte;
+        w[3] = (uint64_t)(uint32_t)e.corrected_left;
+    }
+    if (j == 0) {
+        notes->packets = kept_p;
+        notes->bytes = kept_b;
+        out[0] = (uint64_t)(uint32_t)njobs | (uint64_t)(uint32_t)handed << 32;
+        out[1] = (uint64_t)kept_p;
+        out[2] = (uint64_t)kept_b;
+        out[3] = 0;
+    }
+}
+
+// Launch 3, the job form: the notes are read from scratch; a packet is a record of 40 + pad8(len) bytes at the job's first byte plus the
+// walk's offset; the address is the stream's own, whole
+struct StreamBuild {
+    const StreamPk &K;
+    uint8_t *records;
+    const StreamPkNotes *notes;
+    const pm_rpk::Accepted *acc;
+    const int64_t *recoff;
+    __device__ int64_t total() const { return notes->packets; }
+    __device__ int row_of(int64_t q) const
+    {
+        const int64_t *first = notes->first;
+        return pm_rpk::row_of_packet([first](int i) { return first[i]; }, K.njobs, q);
+    }
+    __device__ BuildItem item(const uint8_t *block, int r, int64_t q) const
+    {
+        const int kind = K.kind[r];
+        const int64_t i = K.acc0[r] + (q - notes->first[r]);
+        pm_rpk::Part p = pm_rpk::part_of(block + K.off[r], kind, K.n[r]);
+        p.addrs = K.addr[r];
+        return BuildItem{p, acc[i], kind, K.crc[r], K.source[r], records + notes->entry[r].first_byte + recoff[i]};
+    }
+    __device__ static int64_t address(const pm_rpk::Part &p, int, int64_t k, int) { return p.addrs[k]; }
+    __device__ static int data_words(int len) { return (len + 7) >> 3; }
+};
+__global__ __launch_bounds__(64) void stream_packets_build_kernel(StreamPk K, const uint8_t *block, uint8_t *records, const StreamPkNotes *notes,
+                                                                  const pm_rpk::Accepted *acc, const int64_t *recoff)
+{
+    packets_build(StreamBuild{K, records, notes, acc, recoff}, block);
 }
 
 // what the launches share in context scratch, cut for `jobs` jobs (or rows)
@@ -1531,6 +1726,64 @@ extern "C" int pm_rows_packets(pm_ctx *ctx, const pm_rowslice_rec *d_recs, const
                        info, acc, all);
     hipLaunchKernelGGL(rows_packets_room_kernel, dim3(1), dim3(kLanes), 0, ctx->stream, nrows, head, entries, capacity);
     hipLaunchKernelGGL(rows_packets_build_kernel, dim3(kBuildWaves), dim3(64), 0, ctx->stream, K, static_cast<const uint8_t *>(d_block), out, info, acc);
+    PM_HIP(hipGetLastError());
+    return PM_OK;
+}
+
+extern "C" int pm_stream_packets(pm_ctx *ctx, const pm_scan_job *h_jobs, int njobs, const int32_t *h_sources, const void *d_block, const int64_t *h_offsets,
+                                 void *d_out, size_t out_bytes, size_t *h_used)
+{
+    PM_CTX(ctx);
+    PM_ARG(h_jobs && njobs >= 1 && njobs <= kScanJobs && d_block && ((uintptr_t)d_block & 7) == 0 && h_offsets && d_out && ((uintptr_t)d_out & 7) == 0 && h_used);
+    StreamPk K;
+    memset(&K, 0, sizeof(K));
+    K.njobs = njobs;
+    // the parts as pm_stream_scan laid them out for the same jobs: what the offsets must be
+    size_t at = 0;
+    int64_t places = 0;
+    for (int j = 0; j < njobs; ++j) {
+        const pm_scan_job &q = h_jobs[j];
+        PM_ARG(q.n >= 0 && q.n <= (int64_t)1 << 29 && q.codec_kind >= -1 && q.codec_kind <= 1 && !q.d_carry);
+        PM_ARG(q.frames == (q.codec_kind == 0) && q.packets == (q.codec_kind == 1) && (q.addrs == 0 || q.addrs == 1));
+        // a job with a codec goes this way by the table of its kind and the stream's addresses
+        PM_ARG(q.codec_kind < 0 || (q.d_addr && ((uintptr_t)q.d_addr & 7) == 0));
+        PM_ARG(h_offsets[j] == (int64_t)at);
+        K.off[j] = (int64_t)at;
+        K.addr[j] = q.d_addr;
+        K.n[j] = (int32_t)q.n;
+        K.acc0[j] = (int32_t)places;
+        K.source[j] = h_sources ? h_sources[j] : j;
+        K.kind[j] = (int8_t)q.codec_kind;
+        K.tol[j] = (int8_t)std::max(-1, std::min(33, q.sync_tol));
+        K.crc[j] = q.il2p_crc != 0;
+        at += (size_t)pm_rows::scan_bytes(q.codec_kind, q.frames, q.packets, q.n) + (q.addrs ? (size_t)PM_SCAN_ADDR_BYTES(q.n) : 0);
+        places += q.codec_kind == 0 ? q.n / 19 + 2 : q.codec_kind == 1 ? q.n / 64 + 2 : 0;
+        PM_ARG(places < INT32_MAX);
+    }
+    // these launches read the block: it must be memory of the device's
+    {
+        hipPointerAttribute_t attr;
+        memset(&attr, 0, sizeof(attr));
+        const hipError_t e = hipPointerGetAttributes(&attr, d_block);
+        if (e != hipSuccess) (void)hipGetLastError();
+        if (e != hipSuccess || (attr.type != hipMemoryTypeDevice && attr.type != hipMemoryTypeManaged))
+            return pm_set_error(PM_ERR_ARG, "pm_stream_packets: d_block is not device memory (the launches read it)");
+    }
+    const size_t front = (size_t)pm_rpk::kStreamHeadBytes + (size_t)pm_rpk::kEntryBytes * (size_t)njobs;
+    *h_used = front;
+    if (out_bytes < front) return pm_set_error(PM_ERR_CAPACITY, "pm_stream_packets: d_out holds %zu bytes, head and entries need %zu", out_bytes, front);
+    const int64_t capacity = (int64_t)((out_bytes - front) & ~(size_t)7);
+    const size_t notes_bytes = (sizeof(StreamPkNotes) + 63) & ~(size_t)63, acc_bytes = ((size_t)places * sizeof(pm_rpk::Accepted) + 63) & ~(size_t)63;
+    if (int rc = pm_scratch_reserve(ctx, notes_bytes + acc_bytes + (size_t)places * sizeof(int64_t) + 64)) return rc;
+    uint8_t *base = static_cast<uint8_t *>(ctx->d_scratch), *out = static_cast<uint8_t *>(d_out);
+    StreamPkNotes *notes = reinterpret_cast<StreamPkNotes *>(base);
+    pm_rpk::Accepted *acc = reinterpret_cast<pm_rpk::Accepted *>(base + notes_bytes);
+    int64_t *recoff = reinterpret_cast<int64_t *>(base + notes_bytes + acc_bytes);
+    const int btune = ctx->tune.bitscan_packet_waves;
+    hipLaunchKernelGGL(stream_packets_walk_kernel, dim3(njobs), dim3(64), 0, ctx->stream, K, static_cast<const uint8_t *>(d_block), notes, acc, recoff);
+    hipLaunchKernelGGL(stream_packets_room_kernel, dim3(1), dim3(64), 0, ctx->stream, njobs, notes, reinterpret_cast<uint64_t *>(out), capacity);
+    hipLaunchKernelGGL(stream_packets_build_kernel, dim3(btune > 0 ? std::min(btune, kBuildWaves) : kBuildWaves), dim3(64), 0, ctx->stream, K,
+                       static_cast<const uint8_t *>(d_block), out + front, notes, acc, recoff);
     PM_HIP(hipGetLastError());
     return PM_OK;
 }

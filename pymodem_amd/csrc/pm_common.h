@@ -55,6 +55,8 @@ struct pm_tuning {
     int pipe_addrs = 0;                // PM_PIPE_ADDRS: pipe_scan, and the scan jobs write address checkpoints: the host stage resolves an address where a decoder asks for one and expands none
     int pipe_beside = 0;               // PM_PIPE_BESIDE: k >= 1: loop_batch.process_recordings_device takes the rows of a sliced engine run in pieces at every k-th mark and decodes them beside the run (implies pipe_scan); 0: behind it
     int pipe_rows_packets = 0;         // PM_PIPE_ROWS_PACKETS: loop_batch.process_recordings_device has the packets of every row whose tables say everything about it finished on the device (pm_rows_packets behind pm_rows_scan; implies pipe_scan, pipe_frames, pipe_packets, pipe_addrs); 0: the codecs make them
+    int pipe_done = 0;                 // PM_PIPE_DONE: a pm_pipe made on this context has the packets of every chain whose frame or packet table says everything about its stream finished on the device (pm_stream_packets behind pm_stream_scan, into the batch's host block; implies pipe_scan, pipe_frames, pipe_packets; the scan parts stay on the device); 0: the codecs make them
+    int pipe_done_room = 0;            // PM_PIPE_DONE_ROOM: with pipe_done, the bytes a group of 64 scan jobs gets for its records in the host block (0: the rule in pm_pipe.hip, done_room); a group that needs more has NO_ROOM chains, which are decoded the existing way
     int pipe_queue_plan = 1;           // PM_PIPE_QUEUE_PLAN: where a pm_pipe makes its streams (pipe_queue_plan in pm_pipe.hip): 1 every demod stream its own, at the lowest priority level; 0 the caller's stream + one plain stream (before the plan)
     int sweep_no_tail = 0;             // PM_SWEEP_NO_TAIL: the matrix-pipe sweep sends every uncertain sample to the list (round 4), none to its own workgroup's exact chain
 };

@@ -233,19 +233,33 @@ PM_IL2P_HD inline int header_count(const uint8_t *b)        // il2p.py:214-290, 
     return count;
 }
 
+// the fields of the 13 descrambled header bytes that decide how long the AX.25 header is: ax25_header and ax25_header_len share them
+PM_IL2P_HD inline int header_type(const uint8_t *b) { return (b[1] & 0x80) >> 7; }
+PM_IL2P_HD inline int header_pid(const uint8_t *b)
+{
+    int pid = 0;
+    for (int i = 0; i < 4; ++i)
+        if (b[i + 1] & 0x40) pid |= 0x8 >> i;
+    return pid;
+}
+PM_IL2P_HD inline unsigned header_pid_byte(int pid)
+{
+    // {0, 0, 0x10, 0x01, 0x06, 0x07, 0x08, 0xC3, 0xC4, 0xCA, 0xCB, 0xCC, 0xCD, 0xCE, 0xCF, 0xF0}
+    return (unsigned)((pid < 8 ? 0xC308070601100000ull : 0xF0CFCECDCCCBCAC4ull) >> (8 * (pid & 7))) & 0xFF;
+}
+// how many bytes ax25_header makes of the 13 header bytes, without making them: two addresses and the control byte, and the PID byte of
+// the types that have one
+PM_IL2P_HD inline int ax25_header_len(const uint8_t *b) { return header_type(b) != 1 ? 0 : 15 + (header_pid_byte(header_pid(b)) != 0); }
 // il2p.py:214-344: the AX.25 header that the 13 descrambled header bytes stand for, into out (16 bytes at the most); returns how many.
 // Type 0 is transparent encapsulation: nothing.  The two small tables are packed into words, a byte an entry: no table in memory.
 PM_IL2P_HD inline int ax25_header(const uint8_t *b, uint8_t *out)
 {
-    const int type = (b[1] & 0x80) >> 7;
-    int pid = 0, ctl = 0;
-    for (int i = 0; i < 4; ++i)
-        if (b[i + 1] & 0x40) pid |= 0x8 >> i;
+    const int type = header_type(b), pid = header_pid(b);
+    int ctl = 0;
     for (int i = 0; i < 7; ++i)
         if (b[i + 5] & 0x40) ctl |= 0x40 >> i;
     enum { UI, S, U, I } kind = (b[0] & 0x40) ? UI : (pid == 0 ? S : (pid == 1 ? U : I));
-    // {0, 0, 0x10, 0x01, 0x06, 0x07, 0x08, 0xC3, 0xC4, 0xCA, 0xCB, 0xCC, 0xCD, 0xCE, 0xCF, 0xF0}
-    const unsigned pid_byte = (unsigned)((pid < 8 ? 0xC308070601100000ull : 0xF0CFCECDCCCBCAC4ull) >> (8 * (pid & 7))) & 0xFF;
+    const unsigned pid_byte = header_pid_byte(pid);
     const bool pf = ctl & 0x40;
     bool cbit = false;
     int nr = 0, ns = 0, op = 0;

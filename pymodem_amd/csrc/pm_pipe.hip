@@ -57,6 +57,9 @@ struct Rec {                             // one recording on its way through
     std::vector<int64_t> off, count;
     std::vector<int64_t> scan_off;                      // per chain: its part of pm_stream_scan's output inside `block` (empty: no scan)
     std::vector<std::vector<int64_t>> full_addr;        // per chain: addresses in full when a step did not fit 16 bits (else empty)
+    // pipe_done, per chain: where its group's pm_stream_packets output begins inside `block`, the chain's job in the group, the group's jobs (empty: not made)
+    std::vector<int64_t> done_off;
+    std::vector<int32_t> done_idx, done_jobs;
     // result
     // the packet rows: a block out of the pipeline's pool, whose rows hold zeros wherever no packet has written (RowBlock)
     struct RowBlock *rowblock = nullptr;
@@ -117,8 +120,8 @@ struct pm_pipe {
     std::vector<hipEvent_t> slot_event;
     // per worker: slicer output blocks on the device
     struct Work {
-        uint8_t *d_out = nullptr, *d_dense = nullptr;
-        size_t out_bytes = 0, dense_bytes = 0, tmp_n = 0, host_bytes = 0;
+        uint8_t *d_out = nullptr, *d_dense = nullptr, *d_scan = nullptr;      // d_scan: pipe_done, the batch's scan parts, which never leave the device
+        size_t out_bytes = 0, dense_bytes = 0, tmp_n = 0, host_bytes = 0, scan_bytes = 0;
         double *d_tmp = nullptr;
         bool reserved = false;
     };
@@ -148,6 +151,9 @@ struct pm_pipe {
     bool frames = false;                 // pipe_frames: scan, and the AX.25 chains' scan jobs write their frames (pm_scan_job.frames), which the host stage queues as they are
     bool addrs = false;                  // pipe_addrs: scan, and every scan job writes its address checkpoints (pm_scan_job.addrs), from which the host stage resolves the few addresses it needs
     bool scan = false;                   // pipe_scan of the context the pipeline was made on: pm_stream_scan behind the slicers, the host stage decodes from its lists
+    bool done = false;                   // pipe_done: frames and packets, the scan parts stay in a device block of the worker's and pm_stream_packets finishes every group of 64 scan jobs into the host block; the host stage copies the records of FINISHED chains and decodes the others from the compact bytes
+    int64_t done_room = 0;               // pipe_done_room: the bytes of records a group gets (0: the rule, done_room())
+    std::atomic<int64_t> done_finished{0}, done_handed{0}, done_status[12] = {};
     bool host_copy = false;              // PM_PIPE_HOST_COPY: the slicers' compact output through a device block and a copy (round 4), not written to the host block by the kernel
     bool skip_decode = false;            // PM_PIPE_SKIP_DECODE (diagnosis only): the host stage decodes nothing -- what the GPU stages alone sustain
     int64_t next_ticket = 0, submitted = 0, finished = 0;   // submitted: tickets handed out (each is in `results` from then on)
@@ -332,6 +338,13 @@ int exact_chain(pm_pipe *p, pm_ctx *side, pm_pipe::Work &w, const Rec &r, int ch
     return pm_fir_signs_f64(side, corr, nc, s.d_lpf, s.ml, p->d_bits[(size_t)r.slot * p->nchains + chain], 0);
 }
 
+// pipe_done: the most bytes of records that a stream of n bytes can come to (include/pymodem_amd.h, pm_pipe_done_stats)
+size_t done_room(int kind, int64_t n)
+{
+    const size_t pad = ((size_t)n + 7) / 8 * 8;
+    return kind == 0 ? pad + 48 * ((size_t)n / 19 + 2) : kind == 1 ? pad + 72 * ((size_t)n / 64 + 2) : 0;
+}
+
 void slice_worker(pm_pipe *p, int wi)
 {
     (void)pthread_setname_np(pthread_self(), "pm-slice");
@@ -462,6 +475,7 @@ void slice_worker(pm_pipe *p, int wi)
         std::shared_ptr<HostBlock> hb;
         double t_c = t_b, t_d = t_b;
         std::vector<int64_t> offs(jobs.size()), scan_offs;
+        size_t block_used = 0;                // the bytes of the batch's host block that the batch takes (the trace prints them)
         if (!rc) {
             size_t dense_cap = 0;
             for (size_t j = 0; j < caps.size(); ++j)
@@ -469,21 +483,42 @@ void slice_worker(pm_pipe *p, int wi)
             // (pm_stream_scan's output goes behind the compact form, into the same block: per recording and chain -- chains that share a
             // slicer job have LFSRs and codecs of their own -- record, list and descrambled bytes, each group of 64 on a 256-byte boundary)
             const size_t nscan = p->scan ? (size_t)nb * nch : 0;
+            size_t scan_cap = 0;
             for (size_t k = 0; k < nscan; ++k) {
                 const int64_t cnt = jobs[(size_t)jidx[k]].count;
-                dense_cap += PM_SCAN_HEAD + (size_t)PM_SCAN_LIST_BYTES(p->chains[k % nch].codec_kind, cnt) + ((size_t)cnt + 7) / 8 * 8;
-                if (p->frames && p->chains[k % nch].codec_kind == 0) dense_cap += (size_t)PM_SCAN_FRAME_TABLE_BYTES(cnt) + (size_t)PM_SCAN_FRAME_AREA_BYTES(cnt);
-                if (p->packets && p->chains[k % nch].codec_kind == 1) dense_cap += (size_t)PM_SCAN_PACKET_TABLE_BYTES(cnt) + (size_t)PM_SCAN_PACKET_AREA_BYTES(cnt);
-                if (p->addrs) dense_cap += (size_t)PM_SCAN_ADDR_BYTES(cnt);
+                scan_cap += PM_SCAN_HEAD + (size_t)PM_SCAN_LIST_BYTES(p->chains[k % nch].codec_kind, cnt) + ((size_t)cnt + 7) / 8 * 8;
+                if (p->frames && p->chains[k % nch].codec_kind == 0) scan_cap += (size_t)PM_SCAN_FRAME_TABLE_BYTES(cnt) + (size_t)PM_SCAN_FRAME_AREA_BYTES(cnt);
+                if (p->packets && p->chains[k % nch].codec_kind == 1) scan_cap += (size_t)PM_SCAN_PACKET_TABLE_BYTES(cnt) + (size_t)PM_SCAN_PACKET_AREA_BYTES(cnt);
+                if (p->addrs) scan_cap += (size_t)PM_SCAN_ADDR_BYTES(cnt);
             }
-            dense_cap += 256 * ((nscan + 63) / 64);
+            scan_cap += 256 * ((nscan + 63) / 64);
+            // (pipe_done: the scan parts stay in a device block of this worker's; what goes behind the compact form instead is, per group of
+            // 64 scan jobs, pm_stream_packets' head, entries and the room for the group's records)
+            std::vector<size_t> group_out;
+            if (p->done) {
+                for (size_t k0 = 0; k0 < nscan; k0 += 64) {
+                    size_t room = 0;
+                    for (size_t k = k0; k < std::min(nscan, k0 + 64); ++k) room += done_room(p->chains[k % nch].codec_kind, jobs[(size_t)jidx[k]].count);
+                    if (p->done_room > 0) room = (size_t)p->done_room & ~(size_t)7;
+                    group_out.push_back(sizeof(pm_stream_packets_head) + sizeof(pm_stream_packets_entry) * std::min<size_t>(64, nscan - k0) + room);
+                    dense_cap += (group_out.back() + 255) & ~(size_t)255;
+                }
+                if (w.scan_bytes < scan_cap) {                   // sized and grown like d_dense: for a full batch at first use
+                    if (w.d_scan) { (void)pm_free(side, w.d_scan); w.d_scan = nullptr; w.scan_bytes = 0; }
+                    void *q = nullptr;
+                    const size_t want = scan_cap * 3 / 2 * (size_t)p->group / (size_t)nb + 4096;
+                    if (!(rc = pm_malloc(side, want, &q))) { w.d_scan = (uint8_t *)q; w.scan_bytes = want; }
+                }
+            } else {
+                dense_cap += scan_cap;
+            }
             // The compact kernel writes the batch's output STRAIGHT into a page-locked host block (the device reaches it over the link:
             // hipHostMalloc memory is mapped) -- no device-side block, no copy operation behind the kernel.  As a copy of its own the
             // 8 MB took 0.2 ms in steady state but 4-12 ms whenever the demod streams had a dozen recordings queued (the first batches
             // of a run, every batch of a short one): the driver's 20-step figure was 0.81 or 1.1 ms per step by the luck of that
             // (gpurun_out r5m; PM_PIPE_HOST_COPY=1 brings the copy back for comparison).
             const bool direct = !p->host_copy;
-            if (!direct && w.dense_bytes < dense_cap) {
+            if (!rc && !direct && w.dense_bytes < dense_cap) {
                 if (w.d_dense) { (void)pm_free(side, w.d_dense); w.d_dense = nullptr; w.dense_bytes = 0; }
                 void *q = nullptr;
                 const size_t want = dense_cap * 3 / 2 * (size_t)p->group / (size_t)nb + 4096;
@@ -526,12 +561,29 @@ void slice_worker(pm_pipe *p, int wi)
                 for (size_t k = 0; k < nscan; ++k) {
                     const pm_pipe_chain &ch = p->chains[k % nch];
                     const pm_slice_job &q = jobs[(size_t)jidx[k]];
+                    // (pipe_done: the addresses in full for pm_stream_packets, and no checkpoints -- the parts never leave the device)
                     sj[k] = pm_scan_job{q.d_data, q.count, ch.lfsr_poly, 0, ch.lfsr_invert, ch.codec_kind, ch.sync_tol, p->frames && ch.codec_kind == 0 ? 1 : 0,
-                                        p->packets && ch.codec_kind == 1 ? 1 : 0, ch.crc, ch.disable_rs, ch.min_dist, p->addrs ? q.d_addr : nullptr, p->addrs ? 1 : 0};
+                                        p->packets && ch.codec_kind == 1 ? 1 : 0, ch.crc, ch.disable_rs, ch.min_dist, p->addrs || p->done ? q.d_addr : nullptr, p->addrs ? 1 : 0};
                 }
+                size_t sat = 0;                                  // pipe_done: where the group's parts begin in the worker's scan block
+                std::vector<int32_t> sources(p->done ? nscan : 0);
+                for (size_t k = 0; k < sources.size(); ++k) sources[k] = p->chains[k % nch].source_decoder;
                 for (size_t j0 = 0; j0 < nscan && !rc; j0 += 64) {
                     const int nj = (int)std::min<size_t>(64, nscan - j0);
                     size_t u = 0;
+                    if (p->done) {
+                        // the parts into the device block, the group's finished packets into the host block: the offsets stay the scan's
+                        uint8_t *const parts = w.d_scan + sat;
+                        rc = pm_stream_scan(side, sj.data() + j0, nj, parts, w.scan_bytes - sat, scan_offs.data() + j0, &u);
+                        sat += (u + 255) & ~(size_t)255;
+                        const size_t out_bytes = group_out[j0 / 64];
+                        if (!rc && at + out_bytes > dst_bytes) rc = pm_set_error(PM_ERR_CAPACITY, "the batch's block holds %zu bytes, the finished packets end at %zu", dst_bytes, at + out_bytes);
+                        if (!rc) rc = pm_stream_packets(side, sj.data() + j0, nj, sources.data() + j0, parts, scan_offs.data() + j0, dst + at, out_bytes, &u);
+                        for (int k = 0; k < nj; ++k) scan_offs[j0 + k] = (int64_t)at;      // (from here on: where the group's output lies)
+                        at += (out_bytes + 255) & ~(size_t)255;
+                        used = at;
+                        continue;
+                    }
                     rc = pm_stream_scan(side, sj.data() + j0, nj, dst + at, dst_bytes - at, scan_offs.data() + j0, &u);
                     for (int k = 0; k < nj; ++k) scan_offs[j0 + k] += (int64_t)at;
                     at += (u + 255) & ~(size_t)255;
@@ -539,6 +591,7 @@ void slice_worker(pm_pipe *p, int wi)
                 }
             }
             t_d = now_ms();
+            block_used = used;
             if (!rc && !direct && hipMemcpyAsync(hb->p, w.d_dense, used, hipMemcpyDeviceToHost, side->stream) != hipSuccess) rc = pm_set_error(PM_ERR_HIP, "copy of the slicer output failed");
             if (!rc && hipStreamSynchronize(side->stream) != hipSuccess) rc = pm_set_error(PM_ERR_HIP, "slicer stream failed");
         }
@@ -546,8 +599,8 @@ void slice_worker(pm_pipe *p, int wi)
         if (rc) (void)hipStreamSynchronize(side->stream);
         const double t1 = now_ms();
         if (p->trace)
-            fprintf(stderr, "[pm_pipe] worker %d batch of %d (first %lld): demod done at %.2f, collected %.2f, sweeps checked +%.2f, sliced +%.2f, on the host +%.2f ms (host block +%.2f, compact enqueued +%.2f, until it is there +%.2f)\n", wi, nb,
-                    (long long)batch[0]->ticket, batch[0]->t_ready - p->t_origin, t0 - p->t_origin, t_a - t0, t_b - t_a, t1 - t_b, t_c - t_b, t_d - t_c, t1 - t_d);
+            fprintf(stderr, "[pm_pipe] worker %d batch of %d (first %lld): demod done at %.2f, collected %.2f, sweeps checked +%.2f, sliced +%.2f, on the host +%.2f ms (host block +%.2f, compact enqueued +%.2f, until it is there +%.2f), %zu bytes of the host block\n", wi, nb,
+                    (long long)batch[0]->ticket, batch[0]->t_ready - p->t_origin, t0 - p->t_origin, t_a - t0, t_b - t_a, t1 - t_b, t_c - t_b, t_d - t_c, t1 - t_d, block_used);
         for (int b = 0; b < nb; ++b) {
             Rec &r = *batch[b];
             if (rc && !r.status) fail(r, rc);
@@ -556,7 +609,17 @@ void slice_worker(pm_pipe *p, int wi)
                 r.off.assign(nch, 0);
                 r.count.assign(nch, 0);
                 r.full_addr.assign(nch, {});
-                if (!scan_offs.empty()) r.scan_off.assign(scan_offs.begin() + (ptrdiff_t)b * nch, scan_offs.begin() + (ptrdiff_t)(b + 1) * nch);
+                if (!scan_offs.empty() && !p->done) r.scan_off.assign(scan_offs.begin() + (ptrdiff_t)b * nch, scan_offs.begin() + (ptrdiff_t)(b + 1) * nch);
+                if (!scan_offs.empty() && p->done) {
+                    r.done_off.assign(scan_offs.begin() + (ptrdiff_t)b * nch, scan_offs.begin() + (ptrdiff_t)(b + 1) * nch);
+                    r.done_idx.resize(nch);
+                    r.done_jobs.resize(nch);
+                    for (int c = 0; c < nch; ++c) {
+                        const size_t k = (size_t)b * nch + c;
+                        r.done_idx[c] = (int32_t)(k % 64);
+                        r.done_jobs[c] = (int32_t)std::min<size_t>(64, (size_t)nb * nch - k / 64 * 64);
+                    }
+                }
                 for (int c = 0; c < nch && !r.status; ++c) {
                     const size_t j = (size_t)jidx[(size_t)b * nch + c];
                     r.off[c] = offs[j];
@@ -613,9 +676,22 @@ void host_worker(pm_pipe *p)
         if (!r.status) {
             std::vector<pm_host_job> jobs(nch);
             int rc = PM_OK;
+            // pipe_done: a chain whose entry is FINISHED has its packets in the block already, as records: no codec, no job
+            std::vector<const pm_stream_packets_entry *> fin(nch, nullptr);
+            std::vector<const uint8_t *> fin_records(nch, nullptr);
+            int64_t st_count[12] = {};
+            for (int c = 0; c < nch && !r.done_off.empty() && !p->skip_decode; ++c) {
+                const uint8_t *out = r.block->p + r.done_off[c];
+                const pm_stream_packets_entry *e = reinterpret_cast<const pm_stream_packets_entry *>(out + sizeof(pm_stream_packets_head)) + r.done_idx[c];
+                if (e->status == PM_ROWS_PACKETS_FINISHED) {
+                    fin[c] = e;
+                    fin_records[c] = out + sizeof(pm_stream_packets_head) + sizeof(pm_stream_packets_entry) * (size_t)r.done_jobs[c] + e->first_byte;
+                }
+                ++st_count[e->status >= 0 && e->status < 12 ? e->status : PM_ROWS_PACKETS_NO_RECORD];
+            }
             for (int c = 0; c < nch && !rc; ++c) {
                 const pm_pipe_chain &ch = p->chains[c];
-                rc = pm_codec_create(ch.codec_kind, ch.crc, ch.disable_rs, ch.min_dist, ch.sync_tol, ch.source_decoder, &codecs[c]);
+                if (!fin[c]) rc = pm_codec_create(ch.codec_kind, ch.crc, ch.disable_rs, ch.min_dist, ch.sync_tol, ch.source_decoder, &codecs[c]);
                 pm_host_job &j = jobs[c];
                 memset(&j, 0, sizeof(j));
                 j.codec = codecs[c];
@@ -659,7 +735,37 @@ void host_worker(pm_pipe *p)
                     j.h_plain = r.kept_plain[c].data();
                 }
             }
-            if (!rc) rc = pm_host_decode_batch(jobs.data(), nch, p->decode_threads);
+            if (!rc && r.done_off.empty()) {
+                rc = pm_host_decode_batch(jobs.data(), nch, p->decode_threads);
+            } else if (!rc) {
+                // the handed chains through the decoders, from the compact bytes; a finished chain's kept_plain by the LFSR alone
+                std::vector<pm_host_job> handed;
+                std::vector<int> handed_chain;
+                for (int c = 0; c < nch; ++c)
+                    if (!fin[c]) {
+                        handed.push_back(jobs[c]);
+                        handed_chain.push_back(c);
+                    }
+                if (!handed.empty()) rc = pm_host_decode_batch(handed.data(), (int)handed.size(), p->decode_threads);
+                for (size_t k = 0; k < handed.size(); ++k) jobs[(size_t)handed_chain[k]].pending = handed[k].pending;
+                for (int c = 0; c < nch && !rc; ++c) {
+                    if (!fin[c]) continue;
+                    jobs[c].pending = fin[c]->packets;
+                    uint64_t reg = 0;
+                    if (p->keep_slices && jobs[c].n) rc = pm_lfsr_unscramble(jobs[c].h_data, jobs[c].n, p->chains[c].lfsr_poly, p->chains[c].lfsr_invert, &reg, r.kept_plain[c].data());
+                }
+                int64_t nfin = 0;
+                for (int c = 0; c < nch; ++c) nfin += fin[c] != nullptr;
+                p->done_finished += nfin;
+                p->done_handed += nch - nfin;
+                for (int k = 1; k < 12; ++k) p->done_status[k] += st_count[k];
+                if (p->trace) {
+                    std::string line = "[pm_pipe] recording " + std::to_string(r.ticket) + ": " + std::to_string(nfin) + " chains finished on the device, handed over by status";
+                    for (int k = 1; k < 12; ++k)
+                        if (st_count[k]) line += " " + std::to_string(k) + ":" + std::to_string(st_count[k]);
+                    fprintf(stderr, "%s\n", line.c_str());
+                }
+            }
             if (p->trace) {
                 std::string line = "[pm_pipe] recording " + std::to_string(r.ticket) + " rc " + std::to_string(rc) + ": slicer bytes / packets per chain";
                 for (int c = 0; c < nch; ++c) line += " " + std::to_string(r.count[c]) + "/" + std::to_string(jobs[c].pending);
@@ -675,7 +781,30 @@ void host_worker(pm_pipe *p)
                 r.rows = r.rowblock ? r.rowblock->rows : nullptr;
                 r.nrows = total;
                 if (!r.rows) rc = pm_set_error(PM_ERR_ARG, "out of host memory for %lld packet rows", (long long)total);
-                if (!rc) rc = pm_codec_fetch_batch_clean(codecs.data(), r.counts.data(), nch, r.rows, p->decode_threads);
+                if (!rc && r.done_off.empty()) {
+                    rc = pm_codec_fetch_batch_clean(codecs.data(), r.counts.data(), nch, r.rows, p->decode_threads);
+                } else if (!rc) {
+                    // chain after chain, in config order: a handed chain's rows from its codec, a finished chain's from its records (the rows
+                    // are clean: a record's head and bytes are all that has to be written)
+                    int64_t at = 0, record_bytes = 0;
+                    for (int c = 0; c < nch && !rc; ++c) {
+                        if (!fin[c]) {
+                            if (r.counts[c]) rc = pm_codec_fetch_batch_clean(&codecs[c], &r.counts[c], 1, r.rows + at, 1);
+                        } else {
+                            const uint8_t *rec = fin_records[c];
+                            for (int64_t k = 0; k < r.counts[c]; ++k) {
+                                pm_packet_head h;
+                                memcpy(&h, rec, sizeof(h));
+                                const size_t len = h.len < 0 ? 0 : h.len > PM_PKT_MAX ? PM_PKT_MAX : (size_t)h.len;
+                                memcpy(&r.rows[at + k], rec, sizeof(h) + len);
+                                rec += sizeof(h) + (len + 7) / 8 * 8;
+                            }
+                            record_bytes += rec - fin_records[c];
+                        }
+                        at += r.counts[c];
+                    }
+                    if (p->trace) fprintf(stderr, "[pm_pipe] recording %lld: %lld bytes of records copied into its rows\n", (long long)r.ticket, (long long)record_bytes);
+                }
                 if (r.rowblock) {                             // the packets' lengths, before anyone else can touch the rows
                     r.rowblock->lens.resize((size_t)total);
                     for (int64_t k = 0; k < total; ++k) {
@@ -744,7 +873,7 @@ int pm_pipe_destroy(pm_pipe *p)
     if (p->h_cells) (void)hipHostFree(p->h_cells);
     for (size_t i = 0; i < std::min(p->work.size(), p->side.size()); ++i) {      // (a create that failed half way: fewer contexts than blocks)
         pm_ctx *s = p->side[i];
-        for (void *q : {(void *)p->work[i].d_out, (void *)p->work[i].d_dense, (void *)p->work[i].d_tmp})
+        for (void *q : {(void *)p->work[i].d_out, (void *)p->work[i].d_dense, (void *)p->work[i].d_scan, (void *)p->work[i].d_tmp})
             if (q) (void)pm_free(s, q);
     }
     for (hipEvent_t e : p->slot_event)
@@ -782,6 +911,12 @@ int pm_pipe_create(pm_ctx *ctx, const pm_pipe_desc *desc, pm_pipe **out)
     p->frames = ctx->tune.pipe_frames != 0;
     p->packets = ctx->tune.pipe_packets != 0;
     p->addrs = ctx->tune.pipe_addrs != 0;
+    p->done = ctx->tune.pipe_done != 0;
+    p->done_room = ctx->tune.pipe_done_room > 0 ? ctx->tune.pipe_done_room : 0;
+    if (p->done) {                                          // frames and packets, and no checkpoints: the parts never leave the device
+        p->frames = p->packets = true;
+        p->addrs = false;
+    }
     p->scan = ctx->tune.pipe_scan != 0 || p->frames || p->packets || p->addrs;
     p->trace = getenv("PM_PIPE_TRACE") != nullptr;
     p->skip_decode = getenv("PM_PIPE_SKIP_DECODE") != nullptr;
@@ -1191,6 +1326,15 @@ int pm_pipe_bitmap(pm_pipe *p, int64_t ticket, int chain, uint64_t *h_words, int
     }
     PM_CTX(p->ctx);
     PM_HIP(hipMemcpy(h_words, p->d_bits[(size_t)slot * p->nchains + p->bit_owner[chain]], (size_t)words * 8, hipMemcpyDeviceToHost));
+    return PM_OK;
+}
+
+int pm_pipe_done_stats(pm_pipe *p, int64_t *h_finished, int64_t *h_handed, int64_t *h_status_counts)
+{
+    if (!p) return pm_set_error(PM_ERR_ARG, "pm_pipe_done_stats: no pipeline");
+    if (h_finished) *h_finished = p->done_finished.load();
+    if (h_handed) *h_handed = p->done_handed.load();
+    for (int k = 0; k < 12 && h_status_counts; ++k) h_status_counts[k] = p->done_status[k].load();
     return PM_OK;
 }
 

@@ -8,6 +8,9 @@
 //          a second hit in the byte in which an attempt ends, a table that is full.
 //   AX.25  Ax25::framed: every listed event with a frame is a packet (a frame longer than a row is cut as pm_codec_fetch cuts it); a row of
 //          fewer than 24 bytes and a bail are handed over.
+// pm_stream_packets (the job form, for pm_pipe) goes by the same rules: its walk launch gives a lane an AX.25 event (ax25_start, ax25_event)
+// and runs il2p_walk as it stands, its records are packet_build_to's with the stream's own addresses and a dense output
+// (tests/stream_packets_core_check.cpp steps that on the host against tests/stream_packets_model.py).
 // A part lies in device memory at a multiple of 8, and so does every piece of it: words are loaded as words.
 #pragma once
 #include <stdint.h>
@@ -24,8 +27,9 @@
 
 namespace pm_rpk {
 
-constexpr int kEntryBytes = 32, kHeadBytes = 16;
+constexpr int kEntryBytes = 32, kHeadBytes = 16, kStreamHeadBytes = 32;
 static_assert(sizeof(pm_rows_packets_entry) == kEntryBytes && sizeof(pm_rows_packets_head) == kHeadBytes && sizeof(pm_packet) % 8 == 0, "the layout of d_out");
+static_assert(sizeof(pm_stream_packets_entry) == kEntryBytes && sizeof(pm_stream_packets_head) == kStreamHeadBytes, "the layout of pm_stream_packets' d_out");
 
 // what a row's walk accepts: IL2P -- the record, the last bit of the attempt's last block (the CRC bytes begin behind it; below 2^32 as
 // every bit of a stream is), the decoder's count of corrected bytes when the packet is queued; AX.25 -- the event, the flag's bit P, 0
@@ -150,30 +154,59 @@ PM_RPK_HD int32_t il2p_walk(const Part &p, int tol, bool crc, int32_t *packets, 
     return PM_ROWS_PACKETS_FINISHED;
 }
 
-// The AX.25 rule
+// The AX.25 rule, in the two steps that a walk of any shape takes: what the stream as a whole says (FINISHED: go on, with `events` listed
+// events to look at), and what one listed event says -- a packet or none, its flag's bit P and its frame's bytes, or a table that cannot be
+// the stream's.  ax25_walk below takes the events one after the other; pm_stream_packets' walk launch gives a lane an event.
+struct Ax25Event {
+    bool take, bad;
+    uint32_t P;
+    int32_t len;
+};
+PM_RPK_HD int32_t ax25_start(const Part &p, int32_t *events)
+{
+    const int64_t n = p.n, places = n / 19 + 2;
+    *events = 0;
+    if (n < 24) return PM_ROWS_PACKETS_SHORT;
+    if ((int64_t)ld64(p.rec + 8) >= 0) return PM_ROWS_PACKETS_BAIL;
+    const int32_t said = (int32_t)ld32(p.rec + 24);
+    *events = said > places ? (int32_t)places : said;
+    return PM_ROWS_PACKETS_FINISHED;
+}
+PM_RPK_HD Ax25Event ax25_event(const Part &p, int32_t e)
+{
+    Ax25Event ev{false, false, 0, (int32_t)ld32(p.table + 8 * (int64_t)e)};
+    if (ev.len > 0) {
+        // (a frame longer than the span between its flags cannot belong to the stream -- pm_codec_decode_framed refuses such a table -- and
+        // hands the row over: nothing is read past the part)
+        const uint32_t P = ld32(p.list + 8 * (int64_t)e), F = ld32(p.list + 8 * (int64_t)e + 4);
+        const int64_t from = F == 0xFFFFFFFFu ? 0 : (int64_t)F;
+        ev.P = P;
+        ev.bad = (int64_t)(P >> 3) >= p.n || from > (int64_t)P || ev.len > ((int64_t)P - from) / 8;
+        ev.take = !ev.bad;
+    }
+    return ev;
+}
 template <class Emit>
 PM_RPK_HD int32_t ax25_walk(const Part &p, int32_t *packets, Emit emit)
 {
-    const int64_t n = p.n, places = n / 19 + 2;
     *packets = 0;
-    if (n < 24) return PM_ROWS_PACKETS_SHORT;
-    if ((int64_t)ld64(p.rec + 8) >= 0) return PM_ROWS_PACKETS_BAIL;
-    int32_t events = (int32_t)ld32(p.rec + 24), count = 0;
-    if (events > places) events = (int32_t)places;
+    int32_t events, count = 0;
+    if (const int32_t status = ax25_start(p, &events)) return status;
     for (int32_t e = 0; e < events; ++e) {
-        const int32_t len = (int32_t)ld32(p.table + 8 * (int64_t)e);
-        if (len > 0) {
-            // (a frame longer than the span between its flags cannot belong to the stream -- pm_codec_decode_framed refuses such a table -- and
-            // hands the row over: nothing is read past the part)
-            const uint32_t P = ld32(p.list + 8 * (int64_t)e), F = ld32(p.list + 8 * (int64_t)e + 4);
-            const int64_t from = F == 0xFFFFFFFFu ? 0 : (int64_t)F;
-            if ((int64_t)(P >> 3) >= n || from > (int64_t)P || len > ((int64_t)P - from) / 8) return PM_ROWS_PACKETS_LONG_FRAME;
-        }
-        if (len > 0) emit(count++, Accepted{(uint32_t)e, ld32(p.list + 8 * (int64_t)e), 0, 0});
+        const Ax25Event ev = ax25_event(p, e);
+        if (ev.bad) return PM_ROWS_PACKETS_LONG_FRAME;
+        if (ev.take) emit(count++, Accepted{(uint32_t)e, ev.P, 0, 0});
     }
     *packets = count;
     return PM_ROWS_PACKETS_FINISHED;
 }
+
+// ---- the dense form (pm_stream_packets): a record is the 40-byte head and the packet's bytes, padded with zeros to a multiple of 8
+PM_RPK_HD int32_t record_bytes(int32_t len) { return 40 + (int32_t)pm_rows::pad8(len < PM_PKT_MAX ? len : PM_PKT_MAX); }
+// the bytes of the packet that IL2P record `r` of a part stands for: the rebuilt AX.25 header, the payload, the two CRC bytes
+PM_RPK_HD int32_t il2p_len(const Part &p, const pm_il2p::Rec &r) { return pm_il2p::ax25_header_len(p.area + r.off) + (int32_t)r.count + 2; }
+// a lane's place among the lanes of a ballot that are set in front of it
+PM_RPK_HD int lanes_before(uint64_t ballot, int lane) { return __builtin_popcountll(ballot & (((uint64_t)1 << lane) - 1)); }
 
 // ---- room: rows take their places in row order; the first whose packets would pass the capacity takes none, nor does any row behind it.
 // incl: the packets of rows 0 .. r as the walks counted them (a sum that only grows, so "passes" stays true from the first such row on)
@@ -224,11 +257,12 @@ PM_RPK_HD HeadWords head_words(int64_t addr, const uint8_t *d, int len, int corr
                       (uint64_t)valid_crc | (uint64_t)header << 32, (uint64_t)(uint32_t)source}};
 }
 
-// One packet, whole, by one thread: what the build launch makes with a wave.  out: the row (sizeof(pm_packet) bytes, every one written).
-PM_RPK_HD void packet_build(const Part &p, int kind, const Accepted &a, bool crc, const uint16_t *steps, int source, uint8_t *out)
+// One packet, whole, by one thread: what the build launch makes with a wave.  addr_of(k): the stream address of data byte k; data_bytes(len):
+// how many bytes follow the 40 of the head in `out`, every one written (zeros behind the packet).
+template <class AddrOf, class DataBytes>
+PM_RPK_HD void packet_build_to(const Part &p, int kind, const Accepted &a, bool crc, AddrOf addr_of, DataBytes data_bytes, int source, uint8_t *out)
 {
     uint8_t *data = out + 40;
-    for (int q = 0; q < PM_PKT_MAX; ++q) data[q] = 0;
     int len, calculated, corrected = a.corrected;
     uint32_t carried;
     int64_t k;
@@ -258,9 +292,20 @@ PM_RPK_HD void packet_build(const Part &p, int kind, const Accepted &a, bool crc
         for (int q = 0; q < len; ++q) data[q] = p.area[at + q];
         k = (int64_t)(a.bit >> 3);
     }
-    const HeadWords h = head_words(pm_addrs::resolve(p.addrs, steps, k), data, len, corrected, calculated, carried, source);
+    for (int q = len, end = data_bytes(len); q < end; ++q) data[q] = 0;
+    const HeadWords h = head_words(addr_of(k), data, len, corrected, calculated, carried, source);
     for (int q = 0; q < 5; ++q)
         for (int i = 0; i < 8; ++i) out[8 * q + i] = (uint8_t)(h.w[q] >> (8 * i));
+}
+// the row form: a whole pm_packet (sizeof(pm_packet) bytes), the address from the part's checkpoints and the row's 16-bit steps
+PM_RPK_HD void packet_build(const Part &p, int kind, const Accepted &a, bool crc, const uint16_t *steps, int source, uint8_t *out)
+{
+    packet_build_to(p, kind, a, crc, [&p, steps](int64_t k) { return pm_addrs::resolve(p.addrs, steps, k); }, [](int) { return (int)PM_PKT_MAX; }, source, out);
+}
+// the dense form: a record of record_bytes(len) bytes, the address the stream's own (pm_scan_job.d_addr: no checkpoints, no steps)
+PM_RPK_HD void record_build(const Part &p, int kind, const Accepted &a, bool crc, const int64_t *addr, int source, uint8_t *out)
+{
+    packet_build_to(p, kind, a, crc, [addr](int64_t k) { return addr[k]; }, [](int len) { return (int)pm_rows::pad8(len); }, source, out);
 }
 
 }  // namespace pm_rpk

@@ -38,6 +38,7 @@ const TuneKey kTuneKeys[] = {
     {"pipe_addrs", "PM_PIPE_ADDRS", &pm_tuning::pipe_addrs}, {"pipe_queue_plan", "PM_PIPE_QUEUE_PLAN", &pm_tuning::pipe_queue_plan},
     {"pipe_beside", "PM_PIPE_BESIDE", &pm_tuning::pipe_beside},
     {"pipe_rows_packets", "PM_PIPE_ROWS_PACKETS", &pm_tuning::pipe_rows_packets},
+    {"pipe_done", "PM_PIPE_DONE", &pm_tuning::pipe_done}, {"pipe_done_room", "PM_PIPE_DONE_ROOM", &pm_tuning::pipe_done_room},
     {"sweep_no_tail", "PM_SWEEP_NO_TAIL", &pm_tuning::sweep_no_tail}, {"afsk_split", "PM_AFSK_SPLIT", &pm_tuning::afsk_split}, {"fused_lds_pad", "PM_FUSED_LDS_PAD", &pm_tuning::fused_lds_pad}, {"sweep_lds_templates", "PM_SWEEP_LDS_TEMPLATES", &pm_tuning::sweep_lds_templates},
 };
 }  // namespace
