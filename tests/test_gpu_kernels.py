@@ -196,7 +196,7 @@ def test_afsk_correlate_bit_exact(ctx, m):
         assert np.array_equal(y.download(), O.afsk_correlate_canon(x, *taps)), (m, n)
 
 
-@pytest.mark.parametrize("groups", [1, 2, 3, 7, 8])
+@pytest.mark.parametrize("groups", [1, 2, 3, 4, 5, 6, 7, 8])
 @pytest.mark.parametrize("m", [1, 2, 3, 5, 40, 60, 61])
 def test_afsk_correlate_group_bit_exact(ctx, groups, m):
     """Shared-mark correlator banks: every output stream equals the single-modem kernel's and the oracle's."""
