@@ -96,7 +96,7 @@ struct pm_pipe {
     std::vector<pm_ctx *> demod;         // demod streams, recordings take turns; the pipeline's own from demod_own on
     size_t demod_own = 0;                // (queue plan 0: 1, demod[0] == ctx)
     std::vector<double *> d_bpf_outs;    // one band-passed stream per demod context
-    pm_bpf8_plan *bpf8 = nullptr;        // the band-pass on the int8 matrix pipe (every sweep certified, <= 177 taps; PM_PIPE_BPF8=0: off)
+    pm_bpf8_plan *bpf8 = nullptr;        // the band-pass on the int8 matrix pipe (every sweep certified, <= 241 taps; PM_PIPE_BPF8=0: off)
     std::vector<pm_lpf8_plan *> lpf8;    // per sweep: its low-pass there too (tones, <= 113 taps; PM_PIPE_LPF8=0: off), else nullptr
     std::vector<hipEvent_t> handover;    // per slot: the point of the caller's stream a recording on a demod stream of the pipeline's starts behind
     std::vector<pm_ctx *> side;          // slicer streams, one per worker
@@ -1014,7 +1014,7 @@ int pm_pipe_create(pm_ctx *ctx, const pm_pipe_desc *desc, pm_pipe **out)
             bool all = true;
             for (int s = 0; s < d.nsweeps; ++s) all = all && p->has_tones[s];
             const char *e = getenv("PM_PIPE_BPF8");
-            if (d.nsweeps && all && d.mb + 15 <= 192 && !(e && e[0] == '0')) {
+            if (d.nsweeps && all && d.mb + 15 <= 256 && !(e && e[0] == '0')) {      // (what pm_bpf8_plan_create takes: three or four blocks of the band)
                 std::vector<double> h((size_t)d.mb);
                 if (hipMemcpy(h.data(), d.d_bpf, h.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess)
                     rc = pm_set_error(PM_ERR_HIP, "pm_pipe_create: reading the band-pass taps back failed");

@@ -17,6 +17,7 @@ import pytest
 
 import fir8_model as F
 from conftest import GOLDEN, tuned
+from fused_shapes import e_combine as _e_combine, rails_signal
 from oracle import oracle as O
 from test_gpu_fir8 import _both
 
@@ -109,12 +110,6 @@ def _sweeps(lines):
     return out
 
 
-def _e_combine(lpf, bpf, gains, m):
-    """The 1e-10 term of the sweep's E (pm_afsk_sweep.h, sweep_bound): every mode's E is at least this."""
-    x_bound = float(np.abs(bpf).sum()) * 32768.0
-    return 1e-10 * float(np.abs(lpf).sum()) * (1.0 + max(gains)) * float(m) * 1.4143 * x_bound, x_bound
-
-
 @pytest.fixture(scope="module")
 def tie():
     audio = _tie_recording()
@@ -187,11 +182,7 @@ def test_both_rails_through_the_executor_at_the_tile_edges():
     mb, ml = len(chains[0][1].input_bpf), len(chains[0][1].output_lpf)
     m0 = max(len(ch[1].mark_correlator_i) for ch in chains)
     least = mb + m0 + ml - 2
-    rng = np.random.default_rng(32768)
-    n = least + 3 * 2048 + 200
-    t = np.arange(n)
-    x = 60000.0 * np.sin(2 * np.pi * np.where((t // 40) % 2 == 0, 1300.0, 2100.0).cumsum() / 48000.0) + 20000.0 * rng.standard_normal(n)
-    base = np.clip(np.rint(x), -32768, 32767).astype(np.int16)
+    base = rails_signal(least + 3 * 2048 + 200)
     assert np.count_nonzero(base == -32768) > 1000 and np.count_nonzero(base == 32767) > 1000
     outs = [1, 2, 20, 21, 63, 64, 65, 84, 85, 255, 256, 257, 276, 2047, 2048, 2049, 2068, 2069, 4096, 4097, 6143, 6144, 6165]
     ctx = pymodem_amd.Context.default()
@@ -230,10 +221,7 @@ def test_uncertain_samples_at_the_ends_of_a_stream_through_the_executor():
     least = len(bpf) + max(m for *_, m in sweeps) + len(lpf) - 2
     n = least + 2 * 2048 + 200
     assert (least, n) == (306, 4602)
-    rng = np.random.default_rng(32768)
-    t = np.arange(n)
-    x = 60000.0 * np.sin(2 * np.pi * np.where((t // 40) % 2 == 0, 1300.0, 2100.0).cumsum() / 48000.0) + 20000.0 * rng.standard_normal(n)
-    audio = np.clip(np.rint(x), -32768, 32767).astype(np.int16)
+    audio = rails_signal(n)
     audio[: least + 64] = 0
     audio[-(least + 64):] = 0
     want = [O.run_chain(O.build_chain(48000, l), audio, canon=True) for l in lines]
